@@ -20,7 +20,14 @@ and its per-document digests are all-gathered over RCCL through the engine's C A
 golden digest of the trace's endContent.  torch.distributed (gloo) is the control plane only:
 the barriers around the timed region and the RCCL unique-id broadcast.
 
-cpu_baseline (rank 0 of an N=1 run only): the oracle's sequential RGA merge (oracle/oracle.c
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: setup, warmup,
+the N timed steps, the digest check, the result line.  `--dump-outputs DIR` also writes what the
+last timed step returned to its caller (dump_outputs below).  Everything else the bench measures
+is behind `--full`: the CPU baseline and config 1, the shuffle / plain-SoA / raw-SoA companion
+lines, the one-lane merges after the timed region that give the per-kernel and roofline figures
+their uncontended launch times, and the timing of the parallel host resolve.
+
+cpu_baseline (--full, rank 0 of an N=1 run only): the oracle's sequential RGA merge (oracle/oracle.c
 orc_merge_many), one document per thread over every CPU this process may run on, on a bounded
 sample of the same documents.  config1 (likewise): the oracle's positional replay (orc_replay,
 one core) of automerge-paper, timed like the reference's upstream closure (main.rs:28-36),
@@ -165,6 +172,28 @@ def log(msg: str) -> None:
     print(msg, file=sys.stderr, flush=True)
 
 
+def u64_limbs(values) -> np.ndarray:
+    """u64 values as float64 rows of four 16-bit limbs, most significant first (exact: a float64
+    holds 53 bits, a digest has 64)."""
+    v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
+    return np.stack([((v >> np.uint64(s)) & np.uint64(0xFFFF)).astype(np.float64)
+                     for s in (48, 32, 16, 0)], axis=1)
+
+
+def dump_outputs(out_dir: str, dig, lens, **more) -> None:  # (dig None: a path without digests)
+    """--dump-outputs: what the last timed step handed to its caller, as <name>.npy in float64.
+    digests: every document's 64-bit digest of its merged text as four 16-bit limbs (docs x 4);
+    lens: every document's merged length.  `more`: further named arrays of a workload.  The
+    inputs are fixed (the committed traces, seeded replicas and generators), so two builds run
+    with the same arguments can be compared file by file.  A few hundred KB at the default size."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"lens": np.asarray(lens).astype(np.float64), **more}
+    if dig is not None:
+        arrays["digests"] = u64_limbs(dig)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.asarray(a, dtype=np.float64))
+
+
 # ---------------------------------------------------------------------------------------------
 # ranks and communication
 # ---------------------------------------------------------------------------------------------
@@ -271,10 +300,11 @@ def rank_env() -> tuple:
 # ---------------------------------------------------------------------------------------------
 # inputs
 # ---------------------------------------------------------------------------------------------
-def load_bases(fugue: bool = False):
+def load_bases(fugue: bool = False, time_parallel: bool = True):
     """Resolve the four traces on the host (untimed setup, like the reference's load at
     main.rs:19): anchor logs + per-trace patches, items, end bytes, golden digest, resolve ms.
-    `fugue`: Fugue anchors (left/right children, in-order document; same endContent)."""
+    `fugue`: Fugue anchors (left/right children, in-order document; same endContent).
+    `time_parallel` (--full): also time the four resolved at once, one host thread each."""
     with open(os.path.join(ROOT, "tests", "golden", "traces.json")) as f:
         golden = json.load(f)
     bases, patches, items, survivors, digests, resolve_ms = [], [], [], [], [], []
@@ -289,9 +319,11 @@ def load_bases(fugue: bool = False):
         survivors.append(golden[name]["end_bytes"])
         digests.append(int(golden[name]["tree_digest"], 16))
     # the same four documents resolved at once, one host thread each (crdt_hip_trace_resolve_many)
-    t0 = time.perf_counter()
-    crdt_hip.Trace.resolve_many(traces, len(traces))
-    parallel_ms = (time.perf_counter() - t0) * 1e3
+    parallel_ms = None
+    if time_parallel:
+        t0 = time.perf_counter()
+        crdt_hip.Trace.resolve_many(traces, len(traces))
+        parallel_ms = (time.perf_counter() - t0) * 1e3
     return {"bases": bases, "patches": patches, "items": items, "survivors": survivors,
             "digests": digests, "resolve_ms": resolve_ms, "resolve_parallel_ms": parallel_ms}
 
@@ -449,6 +481,7 @@ def traces_rank(args, comm, make_batch, inputs) -> dict | None:
     step_s = el_max / args.steps
     res = {
         "batch": batch, "stats": stats, "elapsed": el_max, "step_s": step_s,
+        "last_step": (dig, lens),
         "value": float(allc[:, 0].sum()) / step_s, "digests_ok": digests_ok,
         "per_rank": [{c: int(allc[r, i]) for i, c in enumerate(COUNTERS)} for r in range(world)],
         "items_per_s": float(allc[:, 1].sum()) / step_s,
@@ -550,7 +583,7 @@ def traces_workload(args) -> int:
     ctx = crdt_hip.Context(local)
     comm = Comm(world, rank, ctx)
     t_setup = time.perf_counter()
-    inputs = load_bases(args.order == "fugue")
+    inputs = load_bases(args.order == "fugue", time_parallel=args.full)
     if args.splitter_stride:
         ctx.set_param("splitter_stride", args.splitter_stride)
     ctx.set_param("level1", args.level1)
@@ -588,12 +621,16 @@ def traces_workload(args) -> int:
     if rank == 0:
         batch, stats = res["batch"], res["stats"]
         items_per_gpu = batch.items
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *res["last_step"])
         # Kernel times for the roofline come from merges with ONE lane (untimed, after the timed
         # region): with two lanes a wave's level 1 waits for CUs the other lane's level 0 holds,
         # so its HIP-event interval is not the kernel's own duration (a one-lane rocprofv3
         # kernel trace agrees with these).  The timed step itself ran with args.lanes lanes.
+        # Those merges are runs of their own (--full); a plain run prices the timed merges.
         iso_stats = stats
-        if args.lanes > 1:
+        one_lane = args.full and args.lanes > 1
+        if one_lane:
             ctx.set_param("lanes", 1)
             iso_stats = [batch.merge()[2] for _ in range(3)][1:]
             ctx.set_param("lanes", args.lanes)
@@ -615,6 +652,7 @@ def traces_workload(args) -> int:
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": res["step_s"] * 1e3,
+            "full": bool(args.full),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -637,9 +675,10 @@ def traces_workload(args) -> int:
             "runs_per_gpu": stats[0]["runs"],
             "kernels": rf["kernels"],
             "kernels_source": "one-lane merges after the timed region (uncontended launches)"
-                              if args.lanes > 1 else "the timed merges",
+                              if one_lane else "the timed merges",
             "kernels_ms_with_lanes": rf_lanes,
-            "ms_per_step_1_lane": float(np.mean([s["total_ns"] for s in iso_stats])) / 1e6,
+            "ms_per_step_1_lane": float(np.mean([s["total_ns"] for s in iso_stats])) / 1e6
+                                  if one_lane or args.lanes == 1 else None,
             "roofline": rf["roofline"],
             "rooflines": rf["rooflines"],
             "batched_merge": rf["batched_merge"],
@@ -668,7 +707,7 @@ def traces_workload(args) -> int:
         res = batch = stats = None
     # companion line: the same shard relabelled by a seeded random permutation per replica
     # (SURVEY §8(d) config 3's "seed-r permutation": runs no longer contract)
-    if args.companion_replicas and args.relabel != "shuffle":
+    if args.full and args.companion_replicas and args.relabel != "shuffle":
         ca = argparse.Namespace(replicas=args.companion_replicas, relabel="shuffle", warmup=1,
                                 steps=2)
         cres = traces_rank(ca, comm, make_batch, inputs)
@@ -695,7 +734,7 @@ def traces_workload(args) -> int:
     # companion line: the same headline batch over the plain SoA (no compact list of the non-seq
     # items' parents and keys: the level-0 kernels gather them from the columns), so that the
     # headline's dependence on that one-time index is measured, not assumed
-    if args.plain_companion:
+    if args.full and args.plain_companion:
         ctx.set_param("nsq_list", 0)
         pa = argparse.Namespace(replicas=args.replicas, relabel=args.relabel, warmup=1, steps=3)
         pres = traces_rank(pa, comm, make_batch, inputs)
@@ -721,7 +760,7 @@ def traces_workload(args) -> int:
     # from reference-shaped columns (lamport, agent, deleted, codepoint beside the parents), so
     # the step is priced over the raw SoA, the untimed input encoding included (RGA batches: the
     # raw columns carry no Fugue side)
-    if args.raw_companion and args.order == "rga":
+    if args.full and args.raw_companion and args.order == "rga":
         def make_raw(bases, replicas, relabel, seed):
             b = make_batch(bases, replicas, relabel, seed)
             b.set_raw(True)
@@ -745,7 +784,8 @@ def traces_workload(args) -> int:
         if rank == 0:
             rres["batch"].close()
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:  # (the CPU lines belong to the N=1 run)
+        # (the CPU lines belong to the N=1 run)
+        if args.full and not args.no_cpu_baseline and world == 1:
             threads = args.cpu_threads or host_cpus()["threads"]
             out["cpu_baseline"] = cpu_baseline(inputs["bases"], inputs["patches"],
                                                args.cpu_seconds, threads)
@@ -803,6 +843,8 @@ def side_workload(args) -> int:
     if rank == 0:
         log(f"[bench] {desc}: {batch.items} items, setup {time.perf_counter() - t_setup:.1f} s")
     dig, lens, stats, el = merge_steps(batch, comm, args.warmup, args.steps)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dig, lens)
     ok = int(lens[0]) == expect[1] and (expect[0] is None or int(dig[0]) == expect[0])
     cnt = np.array([batch.items, int(el * 1e9), int(ok)], np.uint64)
     allc = comm.allgather_u64(cnt).reshape(world, 3)
@@ -895,8 +937,11 @@ def downstream_workload(args) -> int:
             else:  # the closure as one device call (crdt_hip_replica_replay)
                 res = init.replay(src)
             per[name] = per.get(name, 0.0) + time.perf_counter() - t0
+            last[name] = res
             ok &= res == (ncp, nbytes, dig)
         return ok
+
+    last: dict = {}  # per trace, what the latest closure returned: (codepoints, bytes, digest)
 
     for _ in range(args.warmup):
         step({})
@@ -908,6 +953,9 @@ def downstream_workload(args) -> int:
         ok &= step(per)
     comm.barrier()
     el = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, [last[n][2] for n in TRACES], [last[n][1] for n in TRACES],
+                     codepoints=[last[n][0] for n in TRACES])
     total_patches = sum(w[1] for w in work)
     allc = comm.allgather_u64(np.array([total_patches, int(el * 1e9), int(ok)], np.uint64))
     allc = allc.reshape(world, 3)
@@ -962,7 +1010,7 @@ def upstream_inc_workload(args) -> int:
         expect.append(up.log.visible_len())
     init = crdt_hip.HipMerge.from_str(t.start_content).log
 
-    def loop(incremental, per_ck, check_text=False):
+    def loop(incremental, per_ck, check_text=False, got=None):
         r = crdt_hip.Replica(ctx, init if init.view().n else None)
         ok, paths = True, 0
         for c, ub in enumerate(chunks):
@@ -974,6 +1022,8 @@ def upstream_inc_workload(args) -> int:
             else:
                 cps, nb, _ = r.merge_len()
             per_ck.append(time.perf_counter() - t0)
+            if got is not None:
+                got.append((cps, nb))
             ok &= cps == expect[c]
         if check_text:  # (untimed: the final document itself, not only its length)
             text = r.merge_inc(text=True)[3] if incremental else r.merge()[0]
@@ -991,11 +1041,16 @@ def upstream_inc_workload(args) -> int:
         t0 = time.perf_counter()
         ok, paths = True, 0
         for _ in range(args.steps):
-            o, p = loop(mode != "full", per_ck)
+            got: list = []
+            o, p = loop(mode != "full", per_ck, got=got)
             ok &= o
             paths += p
         comm.barrier()
         el = time.perf_counter() - t0
+        if rank == 0 and args.dump_outputs and mode == "incremental":
+            # every checkpoint's len() of the last incremental loop: UTF-8 bytes and codepoints
+            dump_outputs(args.dump_outputs, None, [g[1] for g in got],
+                         codepoints=[g[0] for g in got])
         res[mode] = {"ms_per_step": el / args.steps * 1e3, "ok": bool(ok),
                      "len_ms_mean": float(np.mean(per_ck)) * 1e3,
                      "len_ms_median": float(np.median(per_ck)) * 1e3,
@@ -1030,8 +1085,16 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1,
                     help="GPUs of this node; without WORLD_SIZE in the environment, bench.py "
                          "starts this many rank processes itself")
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the CPU baseline and config 1, "
+                         "the shuffle / plain-SoA / raw-SoA companion lines, the one-lane merges "
+                         "behind the per-kernel and roofline figures, the parallel resolve timing "
+                         "(each still subject to its own option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (per-document "
+                         "digests and lengths) as DIR/<name>.npy in float64")
     ap.add_argument("--replicas", type=int, default=4096, help="replicas of each trace per GPU")
     ap.add_argument("--relabel", default="rotate", choices=["none", "rotate", "shuffle"])
     ap.add_argument("--companion-replicas", type=int, default=1024,
@@ -1115,6 +1178,8 @@ def parse_args(argv=None):
                     help="config 5: percent of items whose parent is the previous item "
                          "(0 = uniform random parents, the worst case for gathers)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.order == "fugue":  # (the CPU baseline and the companion merge RGA logs)
         args.no_cpu_baseline = True
         args.companion_replicas = 0

@@ -96,3 +96,30 @@ def test_text_scatter_mode_prices_the_text_kernel():
     assert rf["rooflines"]["text"]["kernel"] == "k_tscatter"
     assert set(rf["rooflines"]) == {"classify", "runs", "doctree", "text", "digest"}
 
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    a = bench.parse_args(["--full", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.dump_outputs == "somewhere"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_exact_float64_arrays(tmp_path):
+    import numpy as np
+    dig = np.array([0, 1, 0xFFFFFFFFFFFFFFFF, 0x0123456789ABCDEF, 1 << 53 | 1], np.uint64)
+    lens = np.array([0, 7, 104852, 1 << 40, 3], np.uint64)
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), dig, lens, codepoints=[1, 2, 3, 4, 5])
+    assert sorted(p.name for p in out.iterdir()) == ["codepoints.npy", "digests.npy", "lens.npy"]
+    limbs = np.load(out / "digests.npy")
+    assert limbs.dtype == np.float64 and limbs.shape == (5, 4)
+    back = np.zeros(5, np.uint64)
+    for col in range(4):  # most significant limb first
+        back = (back << np.uint64(16)) | limbs[:, col].astype(np.uint64)
+    assert np.array_equal(back, dig)
+    got = np.load(out / "lens.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint64), lens)
+    bench.dump_outputs(str(out), None, lens)  # a path without digests writes none
+    assert np.load(out / "lens.npy").shape == (5,)

@@ -8,7 +8,7 @@ st=$?; tail -12 gpurun_out/ga_tests.log; [ $st -eq 0 ] || exit $st
 for rep in 1 2; do
   for lanes in 1 2; do
     for ts in 0 1 2; do
-      timeout -k 10 200 python -u bench.py --no-cpu-baseline --steps 8 --warmup 2 --companion-replicas 0 --config1-seconds 0 \
+      timeout -k 10 200 python -u bench.py --full --no-cpu-baseline --steps 8 --warmup 2 --companion-replicas 0 --config1-seconds 0 \
           --raw-companion 0 --plain-companion 0 --lanes $lanes --text-scatter $ts > gpurun_out/ga.json 2> gpurun_out/ga.err
       st=$?; case $st in 0|1) ;; *) echo "status $st"; tail -5 gpurun_out/ga.err; exit $st;; esac
       python3 -c "import json; d=json.loads(open('gpurun_out/ga.json').read().strip().splitlines()[-1]); print('lanes $lanes ts $ts', round(d['ms_per_step'],3), d['digests_ok'], {k: round(v['ms'],3) for k,v in d['kernels'].items() if v['launches']})"

@@ -8,6 +8,6 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
 st=$?; tail -3 gpurun_out/ks_tests.log; [ $st -eq 0 ] || exit $st
 LIBS="libcrdt_hip_head.so libcrdt_hip.so" ARGS="--lanes 1 --raw-companion 0 --plain-companion 0" bash tools/ab_libs.sh || exit 1
 LIBS="libcrdt_hip_head.so libcrdt_hip.so" ARGS="--raw-companion 0 --plain-companion 0" bash tools/ab_libs.sh
-timeout -k 10 300 python -u bench.py --no-cpu-baseline --companion-replicas 0 --config1-seconds 0 --plain-companion 0 \
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --companion-replicas 0 --config1-seconds 0 --plain-companion 0 \
     > gpurun_out/ks_raw.json 2> gpurun_out/ks_raw.err || exit 1
 python3 -c "import json; d=json.loads(open('gpurun_out/ks_raw.json').read().strip().splitlines()[-1]); r=d['companion_raw_soa']; print('raw', r['ms_per_step'], r['encode_ms'], r['digests_ok'], 'main', d['ms_per_step'], d['digests_ok'])"

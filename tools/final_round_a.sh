@@ -4,7 +4,7 @@
 # and a 1-lane kernel trace.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 R=${ROUND:-r06}
-BENCH=" " bash tools/gpu_round.sh || exit 1
+BENCH="--full" bash tools/gpu_round.sh || exit 1
 cp gpurun_out/bench_1.json gpurun_out/${R}_bench_default.json
 cp gpurun_out/gpu_tests.log gpurun_out/${R}_gpu_tests.log
 ROUND=$R bash tools/profile_round.sh || exit 1

@@ -8,7 +8,7 @@ R=${ROUND:-r02a}
 mkdir -p gpurun_out
 echo "== kernel trace at 4096 (default bench command)"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${R}_kt -o run \
-    -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --companion-replicas 0 \
+    -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --companion-replicas 0 \
     --raw-companion 0 > gpurun_out/${R}_bench_4096.json 2> gpurun_out/${R}_kt.log
 st=$?; echo "status $st"; tail -2 gpurun_out/${R}_kt.log
 case $st in 0) ;; *) exit $st;; esac

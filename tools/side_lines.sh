@@ -22,3 +22,5 @@ run downstream_pcie --workload downstream --pcie --steps 10 --warmup 2
 run upstream_inc --workload upstream_inc --steps 3 --warmup 1
 run downstream_fugue --workload downstream --order fugue --steps 20 --warmup 3
 run shuffle --relabel shuffle --replicas 1024 --steps 3 --warmup 1 --companion-replicas 0 --plain-companion 0
+# FUGUE_LINE=1: the Fugue line of the headline batch, with its plain-SoA companion and one-lane kernels
+[ -z "$FUGUE_LINE" ] || run fugue --full --order fugue --steps 10
