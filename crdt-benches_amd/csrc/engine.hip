@@ -16,6 +16,8 @@
 //                  nibbles, each tile's UTF-8 compacted in slot order; jump bits and the
 //                  tile's parent list from the parents of its non-seq items
 //    k_heads       head bitvector words, per-tile head counts
+//                  (resident RGA batches keep their jump bits with the input encoding, and
+//                  k_classify computes the heads of its tile itself: the static path, L0Args::sjump)
 //    k_tiles_*     exclusive scan of the per-tile (heads, weight) pairs
 //    k_runs        run records (head slot, weight prefix, key, parent run by rank lookup),
 //                  slot-order UTF-8
@@ -83,11 +85,13 @@ enum Ctl {
                     //   exits at once and the host merges the wave again with a fresh plan
 };
 
-// Level-0 scratch cleared in one launch: the wave's ctl words and its jump bitvector.
+// Level-0 scratch cleared in one launch: the wave's ctl words and its jump bitvector.  A wave on
+// the static path (L0Args::sjump) has no bits to clear (nq = 0) and starts its error word from the
+// sticky flag its resident jump bits were built with (`bad`, DeviceLogs::jump word 0).
 __global__ __launch_bounds__(256) void k_clear(uint32_t* __restrict__ ctl, uint4* __restrict__ bits,
-                                               uint32_t nq) {
+                                               uint32_t nq, const uint32_t* __restrict__ bad) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i < 16) ctl[i] = 0;
+    if (i < 16) ctl[i] = (i == C_ERR && bad) ? (*bad & 1u) : 0u;
     for (uint32_t k = i; k < nq; k += gridDim.x * 256) bits[k] = make_uint4(0, 0, 0, 0);
 }
 
@@ -173,6 +177,11 @@ struct L0Args {
     // and key from the columns in slot order (a run's parent run is its document start's run
     // plus the parent's item index).  RGA waves only.
     uint32_t nocon;
+    // 1: jbits are the batch's resident jump bits (DeviceLogs::jump, complete before the merge
+    // starts and read-only in it): k_classify reads no parents and sets no bits, and its first
+    // wave computes the tile's run heads (head_word) in k_heads' place.  Contracted RGA waves
+    // with a list (Engine::static_wave).
+    uint32_t sjump;
 };
 
 constexpr uint32_t kTileBytes = kScanTile * 4;  // worst case: every slot a 4-byte character
@@ -220,10 +229,24 @@ __device__ __forceinline__ uint64_t spread_nib16(uint32_t v) {
 //    nsq item is a run head, and k_runs reads its parent there (coalesced) instead of gathering it.
 // The stream part reads 3 bytes per slot and waits for one round trip; the parent part is one
 // more round trip at the end of the block, hidden behind the other blocks' streams.
+// Static path (L0Args::sjump: a contracted RGA wave whose batch keeps its jump bits with the
+// compact list, Engine::nsq_scatter): the parent part is gone.  The bits are resident and bad
+// parents were flagged when they were built, so the kernel reads no list entry, lists nothing
+// and issues no atomic.  Instead the threads leave their 16-bit nsq and visible masks in LDS,
+// and after the text stage's barrier the first wave (lane = 64-slot word of the tile) loads its
+// resident jump word and computes the tile's head records and head count (head_word, k_heads'
+// logic: a run never crosses a tile, so everything it needs is in this workgroup); k_heads is
+// not launched.
+template <bool STATIC>
+__device__ __forceinline__ void head_word(const L0Args& a, uint32_t wi, bool live, uint2 doc,
+                                          uint64_t nsq, uint64_t vis, uint64_t jw, uint64_t pjump);
+
 __global__ __launch_bounds__(kBlock) void k_classify(L0Args a) {
     __shared__ uint32_t lds[kBlock / 64];
-    __shared__ uint32_t jl[kScanTile / 32];
-    __shared__ uint32_t ll[kScanTile / 32];  // (Fugue) the tile's own left-child bits
+    // (static path: jl and ll hold the threads' 16-bit nsq and visible masks instead, which the
+    // first wave reads back as the tile's 64 words)
+    __shared__ __attribute__((aligned(8))) uint32_t jl[kScanTile / 32];
+    __shared__ __attribute__((aligned(8))) uint32_t ll[kScanTile / 32];  // (Fugue) the tile's own left-child bits
     __shared__ uint2 ldoc[kBlock];  // per thread: its document {base slot, items}
     // (+64: one sink byte per lane for the branch-free ASCII stores below)
     __shared__ __attribute__((aligned(16))) uint8_t sb[kTileBytes + 64];
@@ -321,6 +344,11 @@ __global__ __launch_bounds__(kBlock) void k_classify(L0Args a) {
     uint32_t tot;
     const uint32_t ex = block_excl_scan<kBlock / 64>(((uint32_t)__popc(nsq) << 16) | W, lds, tot);
     const uint32_t tw = tot & 0xFFFFu, T = tot >> 16;
+    if (a.sjump) {
+        // (after the scan's barriers, so past the clearing of jl and ll; read after the next one)
+        reinterpret_cast<uint16_t*>(jl)[threadIdx.x] = (uint16_t)nsq;
+        reinterpret_cast<uint16_t*>(ll)[threadIdx.x] = (uint16_t)vis;
+    }
     if (a.mode == 0 && W == (uint32_t)__popc(vis)) {
         // every visible character of the thread is one UTF-8 byte (nearly always on the traces):
         // 16 unconditional byte stores, a slot without a visible character into the lane's sink
@@ -354,7 +382,13 @@ __global__ __launch_bounds__(kBlock) void k_classify(L0Args a) {
     // (compact list) the tile's first list entries, loaded now that the slot words are dead: they
     // arrive while the text is copied out and the nsq items are listed
     uint32_t ppre[4] = {0u, 0u, 0u, 0u};  // list entries threadIdx.x + j kBlock of the tile
-    if (cl) {
+    // (static path) the first wave's lane = a 64-slot word of the tile: its resident jump word,
+    // loaded now so that it arrives while the text is copied out
+    const uint32_t hwi = tile * (kScanTile / 64) + threadIdx.x;
+    const bool hlive = threadIdx.x < 64u && hwi * 64u < a.nslots;
+    uint64_t hjw = 0;
+    if (a.sjump && hlive) hjw = *reinterpret_cast<const uint64_t*>(a.jbits + 2u * hwi);
+    if (cl && !a.sjump) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint32_t q = nlo + threadIdx.x + (uint32_t)j * kBlock;
@@ -369,6 +403,21 @@ __global__ __launch_bounds__(kBlock) void k_classify(L0Args a) {
     }
     if (cl && T != nhi - nlo && threadIdx.x == 0) atomicOr(&a.ctl[C_ERR], 1u);  // list != flags
     if (a.nocon) return;  // (no contraction: no jump bits; k_runs checks the parents)
+    if (a.sjump) {
+        // static path: the jump bits are resident and the list was checked when they were built
+        // (k_nsq_scatter), so no parent is read and no bit set.  The tile's run heads here, in
+        // k_heads' place: every word they need is in this workgroup (a run never crosses a tile)
+        if (threadIdx.x < 64u) {
+            const uint64_t nw = reinterpret_cast<const uint64_t*>(jl)[threadIdx.x];
+            const uint64_t vw = reinterpret_cast<const uint64_t*>(ll)[threadIdx.x];
+            // the jump bit of the slot before the word: the previous lane's top bit (lane 0 is
+            // the tile's first word, which heads a run whatever came before)
+            const uint32_t up = (uint32_t)__shfl_up((int)(uint32_t)(hjw >> 63), 1);
+            head_word<true>(a, hwi, hlive, ldoc[threadIdx.x * 4u], nw, vw, hjw,
+                            threadIdx.x == 0u ? 1u : up);
+        }
+        return;
+    }
     if (T == 0) return;  // (block-uniform) no nsq item: no jump bit from this tile
     __syncthreads();  // the text stage is stored: its LDS holds the list
     // list entries: tile-local slot, bit 15 = a left child (Fugue)
@@ -462,49 +511,41 @@ __device__ __forceinline__ uint64_t low_mask64(uint32_t b) {
 // still follow their parent's run (rho - 1), whose last item is live by its jump bit.
 // Fugue waves: a head with left children numbers two rows (see kRecTree), and hrec .z and the
 // tile totals count rows, not heads.
-__global__ __launch_bounds__(kBlock) void k_heads(L0Args a) {
-    const uint32_t wi = blockIdx.x * kBlock + threadIdx.x;
+// head_word is the work of one lane (word wi, `live` = inside the wave, `doc` its document, its
+// nsq, visible and jump words, `pjump` = the jump bit of the slot before the word, 1 at a tile's
+// first word), for a whole wave at once: k_heads loads the words k_classify stored; on the static
+// path (STATIC: an RGA wave with contraction, L0Args::sjump) k_classify's first wave calls it with
+// the words of its own tile, and k_heads is not launched.
+template <bool STATIC>
+__device__ __forceinline__ void head_word(const L0Args& a, uint32_t wi, bool live, uint2 doc,
+                                          uint64_t nsq, uint64_t vis, uint64_t jw, uint64_t pjump) {
+    const bool fugue = !STATIC && a.fugue, nocon = !STATIC && a.nocon;
     const uint32_t gs = wi * 64u;
     uint64_t hw = 0, lv = 0, lb = 0, vs = 0, sqh = 0;
-    uint32_t dbase = 0;  // the word's document start (hrec .w: k_runs reads it there)
-    if (gs < a.nslots) {
-        const uint2 doc = a.docs[a.chunk_doc[gs >> a.log2m]];
-        dbase = doc.x;
-        const uint32_t l0 = gs - doc.x, n = doc.y;
-        if (l0 <= n) {
-            const uint64_t nsq = *reinterpret_cast<const uint64_t*>(a.nsqb + (gs >> 4));
-            const uint64_t vis = *reinterpret_cast<const uint64_t*>(a.visb + (gs >> 4));
-            const uint64_t jw = *reinterpret_cast<const uint64_t*>(a.jbits + (gs >> 5));
-            // (a tile's first slot always heads a run: no run crosses a tile, so the text of every
-            // run lies inside one tile's stile segment, which k_doctree stages tile by tile)
-            uint64_t pj = 0;
-            if (l0 > 0)
-                pj = (gs % kScanTile) == 0u
-                         ? 1u
-                         : (a.jbits[(gs >> 5) - 1] >> 31) & 1u;
-            const uint64_t prevj = (jw << 1) | pj;  // bit k = jump(gs + k - 1)
-            const uint64_t item = low_mask64(n + 1u - l0) & ~low_mask64(l0 == 0 ? 1u : 0u);
-            const uint64_t root = l0 == 0 ? 1ull : 0ull;
-            // (Fugue) a slot with left children heads its run and is live: its run node holds them
-            if (a.fugue) lb = *reinterpret_cast<const uint64_t*>(a.lbits + (gs >> 5));
-            hw = root | (item & (nsq | prevj | lb));
-            lv = root | vis | (item & (jw | lb));
-            vs = vis;
-            // a head whose parent is the slot before it (a seq head) makes that slot live: it is
-            // the last item of the head's parent run (RGA: that slot has a jump bit anyway)
-            sqh = hw & item & ~nsq;
-            lv |= sqh >> 1;
-        }
+    const uint32_t dbase = live ? doc.x : 0u;  // the word's document start (hrec .w: k_runs reads it there)
+    const uint32_t l0 = gs - doc.x, n = doc.y;
+    const bool in = live && l0 <= n;
+    if (in) {
+        // (a tile's first slot always heads a run: no run crosses a tile, so the text of every
+        // run lies inside one tile's stile segment, which k_doctree stages tile by tile)
+        const uint64_t pj = l0 > 0 ? pjump : 0ull;
+        const uint64_t prevj = (jw << 1) | pj;  // bit k = jump(gs + k - 1)
+        const uint64_t item = low_mask64(n + 1u - l0) & ~low_mask64(l0 == 0 ? 1u : 0u);
+        const uint64_t root = l0 == 0 ? 1ull : 0ull;
+        // (Fugue) a slot with left children heads its run and is live: its run node holds them
+        if (fugue) lb = *reinterpret_cast<const uint64_t*>(a.lbits + (gs >> 5));
+        hw = root | (item & (nsq | prevj | lb));
+        lv = root | vis | (item & (jw | lb));
+        vs = vis;
+        // a head whose parent is the slot before it (a seq head) makes that slot live: it is
+        // the last item of the head's parent run (RGA: that slot has a jump bit anyway)
+        sqh = hw & item & ~nsq;
+        lv |= sqh >> 1;
     }
     const uint64_t hw0 = hw;  // the run boundaries (before the dead-run drop)
-    if (a.nocon) {
+    if (nocon) {
         // no contraction: every item heads its own run, none is dropped
-        hw = 0;
-        if (gs < a.nslots) {
-            const uint2 doc = a.docs[a.chunk_doc[gs >> a.log2m]];
-            const uint32_t l0 = gs - doc.x, n = doc.y;
-            if (l0 <= n) hw = low_mask64(n + 1u - l0);  // (the document start and its items)
-        }
+        hw = in ? low_mask64(n + 1u - l0) : 0ull;  // (the document start and its items)
     } else {
         // the next word's live slots before its first head keep this word's last run, and so
         // does a seq head in its first slot
@@ -522,7 +563,7 @@ __global__ __launch_bounds__(kBlock) void k_heads(L0Args a) {
         }
         hw &= z;
     }
-    if (a.fugue) {
+    if (fugue) {
         // Fugue: a head with left children numbers two rows only if its run holds visible text;
         // a weightless content row is a leaf that adds nothing, so such a run keeps its tree row
         // alone (its left children, then the last item's right children).  The same segmented
@@ -540,15 +581,35 @@ __global__ __launch_bounds__(kBlock) void k_heads(L0Args a) {
             pm &= pm >> k;
         }
         lb &= z;
-        if (gs < a.nslots) *reinterpret_cast<uint64_t*>(a.lbits + (gs >> 5)) = lb;
+        if (live) *reinterpret_cast<uint64_t*>(a.lbits + (gs >> 5)) = lb;
     }
     // Fugue: a head with left children numbers two run rows (k_runs)
     const uint32_t c = (uint32_t)__popcll(hw) + (uint32_t)__popcll(hw & lb);
     const uint32_t inc = wave_incl_scan(c);
-    if (gs < a.nslots) a.hrec[wi] = make_uint4((uint32_t)hw, (uint32_t)(hw >> 32), inc - c, dbase);
+    if (live) a.hrec[wi] = make_uint4((uint32_t)hw, (uint32_t)(hw >> 32), inc - c, dbase);
     const uint32_t th = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
     const uint32_t tile = wi >> 6;  // 64 words per tile: one wave
     if ((threadIdx.x & 63u) == 0 && tile < a.ntiles) a.tile_hw[tile].x = th;
+}
+
+__global__ __launch_bounds__(kBlock) void k_heads(L0Args a) {
+    const uint32_t wi = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t gs = wi * 64u;
+    const bool live = gs < a.nslots;
+    uint2 doc = make_uint2(0, 0);
+    uint64_t nsq = 0, vis = 0, jw = 0, pj = 0;
+    if (live) {
+        doc = a.docs[a.chunk_doc[gs >> a.log2m]];
+        const uint32_t l0 = gs - doc.x;
+        if (l0 <= doc.y) {
+            nsq = *reinterpret_cast<const uint64_t*>(a.nsqb + (gs >> 4));
+            vis = *reinterpret_cast<const uint64_t*>(a.visb + (gs >> 4));
+            jw = *reinterpret_cast<const uint64_t*>(a.jbits + (gs >> 5));
+            if (l0 > 0)
+                pj = (gs % kScanTile) == 0u ? 1u : (a.jbits[(gs >> 5) - 1] >> 31) & 1u;
+        }
+    }
+    head_word<false>(a, wi, live, doc, nsq, vis, jw, pj);
 }
 
 // Exclusive scan of the tile {heads, weight} pairs: per-4096-tile sums, one workgroup over the
@@ -3815,9 +3876,14 @@ __global__ __launch_bounds__(kBlock) void k_nsq_count(L0Args a, uint32_t* cnt, u
 // the tile's nsq items (k_nsq_count's masks) listed in LDS in slot order (a block scan of the
 // per-thread counts), then their parents and keys read by the whole block and written to the
 // tile's range of the list as consecutive words.
+// With `jb` (the wave's range of the static jump bits, zeroed before; DeviceLogs::jump) every
+// listed parent also gets its jump bit, by k_classify's rule: a parent out of range, or an item
+// that is its own parent, sets the sticky flag `bad` and no bit (so no bit lands outside the
+// item's document); any other parent takes an agent-scope atomicOr (tiles share words).
 __global__ __launch_bounds__(kBlock) void k_nsq_scatter(L0Args a, const uint32_t* pre,
                                                         const uint64_t* mask, uint32_t* out,
-                                                        uint64_t* kout) {
+                                                        uint64_t* kout, uint32_t* jb,
+                                                        uint32_t* bad) {
     __shared__ uint32_t lds[kBlock / 64];
     __shared__ uint16_t lst[kScanTile];
     const uint32_t tile = blockIdx.x, t0 = tile * kScanTile, gs = t0 + threadIdx.x * kScanItems;
@@ -3832,8 +3898,18 @@ __global__ __launch_bounds__(kBlock) void k_nsq_scatter(L0Args a, const uint32_t
         const uint32_t g = t0 + lst[k];
         // the parent as a wave slot (its document's base + its index; the consumers recover the
         // index for their range checks)
-        out[o + k] = a.docs[a.chunk_doc[g >> a.log2m]].x + a.in_parent[g];
+        const uint2 d = a.docs[a.chunk_doc[g >> a.log2m]];
+        const uint32_t pj = a.in_parent[g];
+        out[o + k] = d.x + pj;
         kout[o + k] = a.in_key[g];
+        if (jb) {
+            if (pj > d.y || pj == g - d.x) {
+                *bad = 1u;
+            } else {
+                const uint32_t ps = d.x + pj;  // (<= d.x + d.y: a slot of the item's document)
+                atomicOr(&jb[ps >> 5], 1u << (ps & 31u));
+            }
+        }
     }
 }
 
@@ -3904,10 +3980,11 @@ inline uint32_t ceil_log2(uint64_t x) {
 // =============================================================================================
 void DeviceLogs::release() {
     dfree(parent); dfree(key); dfree(cp);
-    dfree(nsq_par); dfree(nsq_pre); dfree(nsq_key); dfree(nsq_sums); dfree(nsq_mask);
+    dfree(nsq_par); dfree(nsq_pre); dfree(nsq_key); dfree(nsq_sums); dfree(nsq_mask); dfree(jump);
     nsq_items = 0;
     nsq_ok = false;
-    nsq_cap = nsq_pre_cap = nsq_sums_cap = 0;
+    jump_ok = false;
+    nsq_cap = nsq_pre_cap = nsq_sums_cap = jump_cap = 0;
     dfree(docs_rel); dfree(doc_rank); dfree(chunk_doc);
     dfree(raw_lam); dfree(raw_agent); dfree(raw_del); dfree(raw_cp);
     raw = false;
@@ -4000,6 +4077,7 @@ int Engine::plan(DeviceLogs& L, const std::vector<DocInfo>& docs,
     const uint64_t M = 1ull << kDocAlignLog2;  // documents start on 64-slot boundaries
     // (a new slot layout: the compact nsq list, if any, no longer matches it)
     L.nsq_ok = false;
+    L.jump_ok = false;
     L.nsq_items = 0;
     L.log2m = kDocAlignLog2;
     L.docs = docs;
@@ -4471,7 +4549,8 @@ int Engine::clock_mark(StageClock& c, int stage) {
     a0.in_parent = L.parent + w.slot0;                              \
     a0.in_key = L.key + w.slot0;                                    \
     a0.in_cp = L.cp + 3ull * w.slot0;                               \
-    a0.jbits = jbits_;                                              \
+    a0.sjump = static_wave(L, w) ? 1u : 0u;                         \
+    a0.jbits = a0.sjump ? L.jump + DeviceLogs::kJumpHead + (w.slot0 >> 5) : jbits_; \
     a0.nsqb = nsqb_;                                                \
     a0.wnib = wnib_;                                                \
     a0.visb = visb_;                                                \
@@ -4559,12 +4638,15 @@ int Engine::launch_level0(DeviceLogs& L, const Wave& w, bool ord, bool copy_text
     const uint32_t ntiles = a0.ntiles;
     const uint32_t nsums = (ntiles + kScanTile - 1) / kScanTile;
     // jump-bit words (and the left-child bits right after them), in uint4
-    const uint32_t nq = (uint32_t)(jbits_words(w.nslots) / 4) * (L.fugue ? 2u : 1u);
-    k_clear<<<std::min<uint32_t>(grid_for(nq), 2048u), 256, 0, s>>>(ctl_, reinterpret_cast<uint4*>(jbits_), nq);
+    // (static path: the bits are resident, nothing to clear but ctl, whose error word starts
+    // from the flag the bits were built with; k_classify computes the heads)
+    const uint32_t nq = a0.sjump ? 0u : (uint32_t)(jbits_words(w.nslots) / 4) * (L.fugue ? 2u : 1u);
+    k_clear<<<std::max(1u, std::min<uint32_t>(grid_for(nq), 2048u)), 256, 0, s>>>(
+        ctl_, reinterpret_cast<uint4*>(jbits_), nq, a0.sjump ? L.jump : nullptr);
     MARK(-1);
     k_classify<<<ntiles, kBlock, 0, s>>>(a0);
     MARK(S_CLASSIFY);
-    k_heads<<<grid_for(w.nslots / 64), kBlock, 0, s>>>(a0);
+    if (!a0.sjump) k_heads<<<grid_for(w.nslots / 64), kBlock, 0, s>>>(a0);
     if (nsums == 1) {
         k_tiles_one<<<1, kBlock, 0, s>>>(a0);
     } else {
@@ -4864,16 +4946,17 @@ int Engine::launch_tail(DeviceLogs& L, const Wave& w, bool ord, bool fused, Stag
 #undef MARK
 #undef TREEARGS
 
-int Engine::finish_wave(const Wave& w, bool ord, const L1Plan& p, uint32_t rounds,
+int Engine::finish_wave(const Wave& w, bool ord, bool static_l0, const L1Plan& p, uint32_t rounds,
                         const StageClock& ck, const uint32_t* hctl, std::vector<float>& stage_ms,
                         std::vector<uint32_t>& stage_launches) {
     const uint32_t g1 = p.lds1 ? 0u : 1u;
     const bool wt = walk_text(w, ord, p);
     const bool expand_run = !p.fuse && !wt;
     const uint32_t rs = l1_csr_ ? 0u : 1u;
-    // (the runs stage: k_heads, the tile scan in one launch or three, k_runs, k_docmax)
+    // (the runs stage: k_heads unless k_classify computed the heads (the static path), the tile
+    // scan in one launch or three, k_runs, k_docmax)
     const uint64_t ntiles = (w.nslots + kScanTile - 1) / kScanTile;
-    const uint32_t runs_launches = ntiles <= (uint64_t)kScanTile ? 4u : 6u;
+    const uint32_t runs_launches = (ntiles <= (uint64_t)kScanTile ? 4u : 6u) - (static_l0 ? 1u : 0u);
     const uint32_t launches[S_N] = {1, runs_launches, (rs_npassB_ + 2) * g1 * rs, g1, (rs ? 1u : 3u) * g1,
                                     (rs ? rs_npass_ : 1u) * g1, (rs ? 2u : 3u) * g1, g1,
                                     (3 + rounds) * g1, (wt ? 4u : 1u) * g1,
@@ -4982,7 +5065,7 @@ int Engine::run_wave(DeviceLogs& L, uint32_t wi, Mode mode, std::vector<float>& 
         // a sibling group wider than the LDS path sorts: redo the wave on the global path
         return run_wave(L, wi, mode, stage_ms, stage_launches, true);
     }
-    rc = finish_wave(w, ord, p, rounds, ck, hctl, stage_ms, stage_launches);
+    rc = finish_wave(w, ord, static_wave(L, w), p, rounds, ck, hctl, stage_ms, stage_launches);
     if (rc) return rc;
     runs_ += p.R;
     if (!errs && hctl[C_VISITED] != p.R) errs |= 16u;  // unreachable runs: a cycle
@@ -5172,6 +5255,7 @@ int Engine::merge_async_prepare(DeviceLogs& L, AsyncMerge& m, bool timed) {
         m.eng[i]->glds_late = glds_late;
         m.eng[i]->doctree_k32 = doctree_k32;
         m.eng[i]->runs_slots = runs_slots;
+        m.eng[i]->static_jumps = static_jumps;
         m.eng[i]->l1_split = l1_split;
         m.eng[i]->probe_doc_ = probe_doc_;
     }
@@ -5290,7 +5374,8 @@ int Engine::merge_async_finish(DeviceLogs& L, AsyncMerge& m, uint64_t* digests, 
         }
         StageClock ck = m.clocks[wi];
         if (!m.timed) ck.n = 0;
-        int rc = E.finish_wave(w, false, m.plans[wi], 0, ck, hctl, stage_ms, stage_launches);
+        int rc = E.finish_wave(w, false, E.static_wave(L, w), m.plans[wi], 0, ck, hctl, stage_ms,
+                               stage_launches);
         if (rc) return rc;
         runs += hctl[C_RTOTAL];
         E.collect(L, wi, digests, lens, cps, text_bytes);
@@ -5376,6 +5461,7 @@ int Engine::merge_lanes(DeviceLogs& L, Mode mode, uint64_t* digests, uint64_t* l
         eng[i]->glds_late = glds_late;
         eng[i]->doctree_k32 = doctree_k32;
         eng[i]->runs_slots = runs_slots;
+        eng[i]->static_jumps = static_jumps;
         eng[i]->probe_doc_ = probe_doc_;
     }
     std::vector<int> rc(K, CRDT_HIP_OK);
@@ -5586,6 +5672,16 @@ int Engine::nsq_reserve_prefix(DeviceLogs& L) {
         L.nsq_sums_cap = nb;
         gen_++;
     }
+    // the static jump bits and their flag (RGA logs; Fugue logs keep their bits per merge)
+    const uint64_t jw = DeviceLogs::kJumpHead + jbits_words(L.total_slots);
+    if (static_jumps && !L.fugue && jw > L.jump_cap) {
+        dfree(L.jump);
+        L.jump_cap = 0;
+        L.jump_ok = false;
+        HIPCHK(dalloc(&L.jump, jw), "hipMalloc jump bits");
+        L.jump_cap = jw;
+        gen_++;
+    }
     return CRDT_HIP_OK;
 }
 
@@ -5741,14 +5837,21 @@ int Engine::raw_encode(DeviceLogs& L) {
     return CRDT_HIP_OK;
 }
 
-// The list itself, every wave's tiles (launches only).
+// The list itself, every wave's tiles (launches only), and with it the static jump bits of RGA
+// logs (DeviceLogs::jump): zeroed with their flag, then set by the same launches.
 void Engine::nsq_scatter(DeviceLogs& L) {
     const bool ord = false;  // (L0ARGS)
+    const uint64_t jw = DeviceLogs::kJumpHead + jbits_words(L.total_slots);
+    const bool sj = static_jumps && !L.fugue && L.jump && L.jump_cap >= jw;
+    L.jump_ok = false;  // (before L0ARGS: the launches below are not on the static path)
+    if (sj) (void)hipMemsetAsync(L.jump, 0, jw * 4ull, stream);
     for (const Wave& w : L.waves) {
         L0ARGS(a0);
         k_nsq_scatter<<<(uint32_t)((w.nslots + kScanTile - 1) / kScanTile), kBlock, 0, stream>>>(
-            a0, L.nsq_pre + (w.slot0 >> 6), L.nsq_mask + (w.slot0 >> 6), L.nsq_par, L.nsq_key);
+            a0, L.nsq_pre + (w.slot0 >> 6), L.nsq_mask + (w.slot0 >> 6), L.nsq_par, L.nsq_key,
+            sj ? L.jump + DeviceLogs::kJumpHead + (w.slot0 >> 5) : nullptr, L.jump);
     }
+    L.jump_ok = sj;
 }
 
 int Engine::nsq_reserve(DeviceLogs& L) {

@@ -132,6 +132,16 @@ struct DeviceLogs {
     uint64_t nsq_cap = 0, nsq_pre_cap = 0, nsq_sums_cap = 0;
     uint32_t* nsq_sums = nullptr;  // (scan scratch)
     uint64_t* nsq_mask = nullptr;  // (the nsq items of every 64-slot chunk, for the scatter)
+    // Static jump bits (Engine::static_jumps, RGA logs with a list): one allocation, word 0 the
+    // sticky "bad parent" flag (a listed parent out of range, or an item that is its own parent),
+    // from word kJumpHead on one bit per slot of the whole slot space, "the slot has a child that
+    // is not the next slot".  A function of the parent column alone, so it is part of the input
+    // encoding: k_nsq_scatter sets the bits with the list (Engine::nsq_scatter) and the merges
+    // only read them.  A wave's bits start at jump + kJumpHead + (slot0 >> 5).
+    static constexpr uint64_t kJumpHead = 4;
+    uint32_t* jump = nullptr;
+    uint64_t jump_cap = 0;   // words allocated
+    bool jump_ok = false;    // the bits match the list (set with it; plan() clears it)
     // Raw SoA mode (Engine::raw_keep, the companion line that prices the input encoding): the
     // reference-shaped columns beside the parent column, lamport u32, agent u16, deleted u8 and
     // codepoint u32 per slot; every merge first derives the key, the codepoint word with its
@@ -183,6 +193,14 @@ public:
     // the rebuild's launches cost more than the gathers it saves, measured on the downstream
     // closures), 2 = every replica too, 0 = never (level 0 gathers the columns)
     uint32_t nsq_list = 1;
+    // 1: RGA logs with a list keep their jump bits resident (DeviceLogs::jump) and level 0 takes
+    // the static path on contracted waves: k_clear clears ctl only, k_classify sets no jump bits
+    // and computes the run heads of its tile itself (no k_heads launch); 0: every merge rebuilds
+    // the bits in k_classify and runs k_heads
+    uint32_t static_jumps = 1;
+    bool static_wave(const DeviceLogs& L, const Wave& w) const {
+        return static_jumps && L.nsq_ok && L.jump && L.jump_ok && !L.fugue && !w.nocon;
+    }
     static constexpr uint64_t kNsqReplicaSlots = 1ull << 22;
     // run contraction of RGA waves: 0 = by the wave's input (no contraction when at least
     // kNoconShare of its items lack the previous-slot flag), 1 = always, 2 = never
@@ -419,8 +437,9 @@ private:
     int launch_tail(DeviceLogs& L, const Wave& w, bool ord, bool fused, StageClock& ck,
                     uint32_t* hblock);
     // After the wave's stream has drained: stage times, launch counts.
-    int finish_wave(const Wave& w, bool ord, const L1Plan& p, uint32_t rounds, const StageClock& ck,
-                    const uint32_t* hctl, std::vector<float>& stage_ms,
+    // (static_l0: the wave took level 0's static path, Engine::static_wave)
+    int finish_wave(const Wave& w, bool ord, bool static_l0, const L1Plan& p, uint32_t rounds,
+                    const StageClock& ck, const uint32_t* hctl, std::vector<float>& stage_ms,
                     std::vector<uint32_t>& stage_launches);
     int run_wave(DeviceLogs& L, uint32_t wi, Mode mode, std::vector<float>& stage_ms,
                  std::vector<uint32_t>& stage_launches, bool force_global = false);
