@@ -50,7 +50,8 @@ EXPORTS = [
     "crdt_hip_replica_merge", "crdt_hip_comm_unique_id", "crdt_hip_comm_init",
     "crdt_hip_allgather_u64", "crdt_hip_comm_destroy", "crdt_hip_xxh64",
     "crdt_hip_tree_digest", "crdt_hip_merge_len", "crdt_hip_replica_merge_len",
-    "crdt_hip_replica_replay",
+    "crdt_hip_replica_replay", "crdt_hip_oplog_join", "crdt_hip_replica_join",
+    "crdt_hip_join_stats",
 ]
 
 
@@ -129,6 +130,7 @@ def lib() -> C.CDLL:
         "crdt_hip_oplog_version": (u64, [vp]),
         "crdt_hip_oplog_encode_from": (i32, [vp, u64, vp, sz, P(sz)]),
         "crdt_hip_oplog_apply_update": (i32, [vp, vp, sz]),
+        "crdt_hip_oplog_join": (i32, [vp, P(View), P(u32), P(u32)]),
         "crdt_hip_trace_load": (i32, [C.c_char_p, P(vp)]),
         "crdt_hip_trace_free": (None, [vp]),
         "crdt_hip_trace_len": (sz, [vp]),
@@ -165,6 +167,8 @@ def lib() -> C.CDLL:
         "crdt_hip_updates_free": (i32, [vp]),
         "crdt_hip_replica_apply_resident": (i32, [vp, vp, vp]),
         "crdt_hip_replica_info": (i32, [vp, P(u64), P(u64), P(u64)]),
+        "crdt_hip_replica_join": (i32, [vp, vp, vp, P(u32), P(u32)]),
+        "crdt_hip_join_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge": (i32, [vp, vp, vp, sz, P(sz), P(u64)]),
         "crdt_hip_replica_merge_len": (i32, [vp, vp, P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge_inc": (i32, [vp, vp, vp, sz, P(sz), P(u64), P(u32)]),
@@ -277,6 +281,21 @@ class OpLog:
         h = C.c_void_p()
         _check(lib().crdt_hip_oplog_clone(self._h, C.byref(h)))
         return OpLog(h)
+
+    def set_agent(self, agent: int) -> None:
+        """The agent id of this log's later local inserts: a fork sets its own on its clone, so
+        that (lamport, agent) identifies its items (crdt_hip_oplog_set_agent)."""
+        _check(lib().crdt_hip_oplog_set_agent(self._h, agent))
+
+    def join(self, other) -> tuple:
+        """State-based merge (crdt_hip_oplog_join): this log <- this log U `other` (an OpLog,
+        LogArrays or LogFile) by item identity (lamport, agent).  Returns (items appended, items
+        this log held that the join tombstoned); a rejected join raises and changes nothing."""
+        v, keep = _as_view(other)
+        a, t = C.c_uint32(), C.c_uint32()
+        _check(lib().crdt_hip_oplog_join(self._h, C.byref(v), C.byref(a), C.byref(t)))
+        del keep
+        return int(a.value), int(t.value)
 
     def insert(self, pos: int, text: str) -> None:
         b = text.encode("utf-8")
@@ -480,6 +499,14 @@ class Context:
 
     def set_param(self, key: str, value: int) -> None:
         _check(lib().crdt_hip_set_param(self._h, key.encode(), value), self._h)
+
+    def join_stats(self) -> dict:
+        """What this context's last Replica.join observed (crdt_hip_join_stats)."""
+        p, t, c, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().crdt_hip_join_stats(self._h, C.byref(p), C.byref(t), C.byref(c),
+                                         C.byref(ns)), self._h)
+        return {"prefix_slots": int(p.value), "table_slots": int(t.value),
+                "table_capacity": int(c.value), "device_ns": int(ns.value)}
 
     def merge(self, log) -> tuple:
         """Merged document: (utf8 bytes, tree digest)."""
@@ -696,6 +723,16 @@ class Replica:
         """Apply a batch already in HBM (crdt_hip_replica_apply_resident): no PCIe transfer."""
         _check(lib().crdt_hip_replica_apply_resident(self.ctx._h, self._h, batch._h), self.ctx._h)
 
+    def join(self, other: "Replica") -> tuple:
+        """State-based merge on the device (crdt_hip_replica_join): this replica <- this replica U
+        `other` by item identity (lamport, agent); `other` is unchanged.  Returns (items appended,
+        items this replica held that the join tombstoned); a rejected join raises and changes
+        nothing."""
+        a, t = C.c_uint32(), C.c_uint32()
+        _check(lib().crdt_hip_replica_join(self.ctx._h, self._h, other._h, C.byref(a),
+                                           C.byref(t)), self.ctx._h)
+        return int(a.value), int(t.value)
+
     def info(self) -> tuple:
         """(items, visible codepoints, visible UTF-8 bytes)."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -810,6 +847,11 @@ class HipMerge:
     def apply_update(self, update: bytes) -> None:
         self.log.apply_update(update)
 
+    def merge_from(self, other: "HipMerge") -> tuple:
+        """`Downstream for Automerge`'s apply_update(&mut self, other: &Self) = doc.merge(other)
+        (rope.rs:234-236): take every op of a divergent replica (OpLog.join)."""
+        return self.log.join(other.log)
+
 
 class HipDownstream:
     """`Downstream` (/root/reference/src/rope.rs:185-191) with the replica on the device.
@@ -845,6 +887,13 @@ class HipDownstream:
         if self.pending:
             self.replica.apply_updates(self.pending)
             self.pending = []
+
+    def merge_from(self, other: "HipDownstream") -> tuple:
+        """doc.merge(other) (rope.rs:234-236) on the device: both replicas decode their queued
+        updates, then this one takes every item of the other (Replica.join)."""
+        self.flush()
+        other.flush()
+        return self.replica.join(other.replica)
 
     def text(self) -> str:
         self.flush()

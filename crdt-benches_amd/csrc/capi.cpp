@@ -31,6 +31,7 @@ struct crdt_hip_ctx {
     // replay sessions (crdt_hip_replica_replay): the work replica and learnt sizes per
     // (initial replica, update batch), most recent first
     std::vector<std::unique_ptr<crdt::ReplayState>> replays;
+    crdt::JoinStats last_join;  // what the last crdt_hip_replica_join observed
 };
 struct crdt_hip_oplog {
     crdt::OpLog log;
@@ -361,6 +362,19 @@ int crdt_hip_oplog_apply_update(crdt_hip_oplog* log, const uint8_t* buf, size_t 
     return guard(nullptr, [&] {
         std::string e = log->log.apply_update(buf, len);
         return e.empty() ? 0 : set_err(nullptr, CRDT_HIP_EINVAL, e);
+    });
+}
+int crdt_hip_oplog_join(crdt_hip_oplog* dst, const crdt_hip_oplog_view* src, uint32_t* added,
+                        uint32_t* tombstoned) {
+    if (!dst) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    int rc = check_view(nullptr, src);
+    if (rc) return rc;
+    return guard(nullptr, [&] {
+        std::string e;
+        const int jrc = dst->log.join(src->n, src->parent, src->origin_right, src->lamport,
+                                      src->agent, src->deleted, src->cp, src->side, added,
+                                      tombstoned, e);
+        return jrc ? set_err(nullptr, jrc, e) : 0;
     });
 }
 
@@ -838,6 +852,25 @@ int crdt_hip_replica_apply_resident(crdt_hip_ctx* ctx, crdt_hip_replica* r,
     return guard(ctx, [&] {
         return from_engine(ctx, crdt::replica_apply_resident(ctx->eng, r->r, u->u));
     });
+}
+int crdt_hip_replica_join(crdt_hip_ctx* ctx, crdt_hip_replica* dst, const crdt_hip_replica* src,
+                          uint32_t* added, uint32_t* tombstoned) {
+    if (!ctx || !dst || !src) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (dst->ctx != ctx || src->ctx != ctx)
+        return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    return guard(ctx, [&] {
+        return from_engine(ctx, crdt::replica_join(ctx->eng, dst->r, src->r, added, tombstoned,
+                                                   &ctx->last_join));
+    });
+}
+int crdt_hip_join_stats(const crdt_hip_ctx* ctx, uint64_t* prefix_slots, uint64_t* table_slots,
+                        uint64_t* table_capacity, uint64_t* device_ns) {
+    if (!ctx) return set_err(nullptr, CRDT_HIP_EINVAL, "null context");
+    if (prefix_slots) *prefix_slots = ctx->last_join.prefix;
+    if (table_slots) *table_slots = ctx->last_join.table_slots;
+    if (table_capacity) *table_capacity = ctx->last_join.table_cap;
+    if (device_ns) *device_ns = ctx->last_join.device_ns;
+    return 0;
 }
 int crdt_hip_replica_info(const crdt_hip_replica* r, uint64_t* items,
                           uint64_t* visible_codepoints, uint64_t* visible_bytes) {

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "crdt_hip.h"
 #include "util.hpp"
 
 namespace crdt {
@@ -849,6 +850,134 @@ std::string OpLog::apply_update(const uint8_t* buf, size_t len) {
         mark_deleted(id);
     }
     return "";
+}
+
+// ---- state-based merge -------------------------------------------------------------------------
+namespace {
+// Identity (lamport << 16 | agent) -> item id, open addressing over a power of two of at least
+// twice the items (the device join's table, join.hip, on the host).
+struct IdTable {
+    std::vector<uint32_t> slot;
+    uint32_t mask = 0;
+    explicit IdTable(uint64_t items) {
+        uint64_t c = 64;
+        while (c < 2 * items) c <<= 1;
+        slot.assign(c, 0u);  // 0: free (ids start at 1)
+        mask = (uint32_t)(c - 1);
+    }
+    static uint32_t hash(uint64_t k) {
+        k ^= k >> 29;
+        k *= 0x9E3779B97F4A7C15ull;
+        return (uint32_t)(k >> 32);
+    }
+    // The id holding key k, or 0; `key_of(id)` gives the key of a stored id.
+    template <class K>
+    uint32_t find(uint64_t k, K&& key_of) const {
+        for (uint32_t h = hash(k) & mask;; h = (h + 1u) & mask) {
+            const uint32_t e = slot[h];
+            if (!e || key_of(e) == k) return e;
+        }
+    }
+    // Stores id under k; returns the id that already held k (then nothing is stored), or 0.
+    template <class K>
+    uint32_t insert(uint64_t k, uint32_t id, K&& key_of) {
+        for (uint32_t h = hash(k) & mask;; h = (h + 1u) & mask) {
+            const uint32_t e = slot[h];
+            if (!e) {
+                slot[h] = id;
+                return 0;
+            }
+            if (key_of(e) == k) return e;
+        }
+    }
+};
+}  // namespace
+
+int OpLog::join(uint32_t ns, const uint32_t* s_parent, const uint32_t* s_oright,
+                const uint32_t* s_lamport, const uint16_t* s_agent, const uint8_t* s_deleted,
+                const uint32_t* s_cp, const uint8_t* s_side, uint32_t* added,
+                uint32_t* tombstoned, std::string& err) {
+    if (added) *added = 0;
+    if (tombstoned) *tombstoned = 0;
+    if (fugue || s_side) {
+        err = "join of a Fugue log is not supported (RGA logs only)";
+        return CRDT_HIP_EINVAL;
+    }
+    const uint32_t nd = size();
+    auto dkey = [&](uint32_t id) { return ((uint64_t)lamport[id - 1] << 16) | agent[id - 1]; };
+    auto skey = [&](uint32_t id) { return ((uint64_t)s_lamport[id - 1] << 16) | s_agent[id - 1]; };
+    // ---- validate: nothing changes before every check has passed -------------------------------
+    IdTable dt(nd), st(ns);
+    for (uint32_t id = 1; id <= nd; ++id) {
+        if (parent[id - 1] >= id) {
+            err = "join: an item's parent does not precede it";
+            return CRDT_HIP_EBADLOG;
+        }
+        if (dt.insert(dkey(id), id, dkey)) {
+            err = "join: two items of the destination share an identity (lamport, agent)";
+            return CRDT_HIP_EBADLOG;
+        }
+    }
+    // src id -> id in this log (new items: nd + 1 + rank in src's slot order)
+    std::vector<uint32_t> mp((size_t)ns + 1);
+    mp[0] = 0;
+    uint32_t nnew = 0;
+    for (uint32_t id = 1; id <= ns; ++id) {
+        if (s_parent[id - 1] >= id) {
+            err = "join: an item's parent does not precede it";
+            return CRDT_HIP_EBADLOG;
+        }
+        const uint64_t k = skey(id);
+        if (st.insert(k, id, skey)) {
+            err = "join: two items of the source share an identity (lamport, agent)";
+            return CRDT_HIP_EBADLOG;
+        }
+        const uint32_t d = dt.find(k, dkey);
+        mp[id] = d ? d : nd + 1u + nnew++;
+    }
+    if ((uint64_t)nd + nnew >= 0x7FFFFFF0ull) {
+        err = "op log too large";
+        return CRDT_HIP_ERANGE;
+    }
+    uint32_t ntomb = 0, ndel_new = 0;
+    for (uint32_t id = 1; id <= ns; ++id) {
+        const uint32_t d = mp[id];
+        if (d > nd) {
+            ndel_new += s_deleted[id - 1] != 0;
+            continue;
+        }
+        if ((cp[d - 1] ^ s_cp[id - 1]) & 0x1FFFFFu) {  // (codepoints: the device keeps 21 bits)
+            err = "join: an item both logs hold has another codepoint in each";
+            return CRDT_HIP_EBADLOG;
+        }
+        if (parent[d - 1] != mp[s_parent[id - 1]]) {
+            err = "join: an item both logs hold has another parent in each";
+            return CRDT_HIP_EBADLOG;
+        }
+        ntomb += s_deleted[id - 1] && !deleted[d - 1];
+    }
+    // ---- apply (src may be a view of this very log: then nothing is new and no column grows) ---
+    if (nnew) reserve((size_t)nd + nnew, del_ops.size() + ntomb + ndel_new);
+    for (uint32_t id = 1; id <= ns; ++id) {
+        const uint32_t d = mp[id];
+        if (d <= nd) {
+            if (s_deleted[id - 1] && !deleted[d - 1]) {
+                del_ops.push_back(d);
+                mark_deleted(d);
+            }
+            continue;
+        }
+        // origin_right: an item id is translated like a parent; 0 and NIL (or anything beyond
+        // src's ids) stay as they are
+        const uint32_t o = s_oright ? s_oright[id - 1] : NIL;
+        const uint8_t del = s_deleted[id - 1] ? 1 : 0;
+        push_item(mp[s_parent[id - 1]], o && o <= ns ? mp[o] : o, s_lamport[id - 1],
+                  s_agent[id - 1], del, s_cp[id - 1]);
+        if (del) del_ops.push_back(d);
+    }
+    if (added) *added = nnew;
+    if (tombstoned) *tombstoned = ntomb;
+    return CRDT_HIP_OK;
 }
 
 }  // namespace crdt

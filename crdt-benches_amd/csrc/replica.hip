@@ -77,20 +77,6 @@ __device__ __forceinline__ uint32_t block_excl_max(uint32_t x, uint32_t* lds, ui
     return max(off, lane ? prev : 0u);
 }
 
-// Sum of x over the block, valid in thread 0 (a device-wide counter then takes one atomic per
-// block: thousands of same-address atomics, one per wave, serialise at the L2 and cost more
-// than the decode itself).
-__device__ __forceinline__ uint32_t block_sum_t0(uint32_t x, uint32_t* lds) {
-    x = wave_sum(x);
-    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = x;
-    __syncthreads();
-    uint32_t t = 0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < kUB / 64; ++i) t += lds[i];
-    __syncthreads();
-    return t;
-}
-
 struct UpdArgs {
     const uint32_t* buf;  // the batch, as words (every update starts 4-aligned)
     const uint64_t* off;  // n + 1 byte offsets
@@ -264,7 +250,7 @@ __global__ __launch_bounds__(kUB) void k_upd_items(UpdArgs a) {
     if (err) atomicOr((unsigned long long*)&a.ctl[U_ERR], (unsigned long long)err);
     if (WRITE) {
         __shared__ uint32_t red[kUB / 64];
-        const uint32_t s0 = block_sum_t0(add_cp, red), s1 = block_sum_t0(add_b, red);
+        const uint32_t s0 = block_sum_t0<kUB / 64>(add_cp, red), s1 = block_sum_t0<kUB / 64>(add_b, red);
         if (threadIdx.x == 0 && s0) {
             atomicAdd((unsigned long long*)&a.ctl[U_ADD_CP], (unsigned long long)s0);
             atomicAdd((unsigned long long*)&a.ctl[U_ADD_B], (unsigned long long)s1);
@@ -302,7 +288,7 @@ __global__ __launch_bounds__(kUB) void k_upd_dels(UpdArgs a) {
     if (err) atomicOr((unsigned long long*)&a.ctl[U_ERR], (unsigned long long)err);
     if (WRITE) {
         __shared__ uint32_t red[kUB / 64];
-        const uint32_t s0 = block_sum_t0(del_cp, red), s1 = block_sum_t0(del_b, red);
+        const uint32_t s0 = block_sum_t0<kUB / 64>(del_cp, red), s1 = block_sum_t0<kUB / 64>(del_b, red);
         if (threadIdx.x == 0 && s0) {
             atomicAdd((unsigned long long*)&a.ctl[U_DEL_CP], (unsigned long long)s0);
             atomicAdd((unsigned long long*)&a.ctl[U_DEL_B], (unsigned long long)s1);

@@ -160,6 +160,22 @@ int replica_replay(Engine& E, const Replica& init, const UpdateBatch& ub, Replay
 int replica_merge(Engine& E, Replica& r, std::vector<uint8_t>* text, uint64_t* len,
                   uint64_t* digest, crdt_hip_stats* st, uint64_t* cps = nullptr);
 
+// What the last join observed (crdt_hip_join_stats; tools/join_time.py reports it).
+struct JoinStats {
+    uint64_t prefix = 0;       // slots of the common prefix (mapped to themselves, in no table)
+    uint64_t table_slots = 0;  // dst slots past the prefix, the entries of the identity table
+    uint64_t table_cap = 0;    // its capacity (a power of two >= twice the entries)
+    uint64_t device_ns = 0;    // summed device time of the join's kernels (HIP events)
+};
+// State-based merge (join.hip): dst <- dst U src by item identity (lamport, agent), the
+// reference's `Downstream for Automerge` apply_update(&mut self, other: &Self) = doc.merge(other)
+// (rope.rs:234-236).  Items of src that dst lacks are appended in src's slot
+// order with their parents translated to dst's ids; an item both hold is tombstoned if either
+// has it tombstoned.  *added: items appended; *tombstoned: items dst held that the join
+// tombstoned.  Validated first: a rejected join (EBADLOG) changes nothing.  RGA replicas only.
+int replica_join(Engine& E, Replica& dst, const Replica& src, uint32_t* added,
+                 uint32_t* tombstoned, JoinStats* stats = nullptr);
+
 // Incremental merge (incr.hip): the merged text (may be null), its UTF-8 bytes and codepoints;
 // *path = 1 when only the items appended since the previous merge_inc were ranked, 0 for a
 // full merge (the first call, a concurrent update, more than kIncMax new items, Fugue).

@@ -48,6 +48,21 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* lds, u
     return off + inc - x;
 }
 
+// Sum of x over the block's threads (NW waves), valid in thread 0 (a device-wide counter then
+// takes one atomic per block: thousands of same-address atomics, one per wave, serialise at the
+// L2 and cost more than the kernels that count with them).
+template <int NW>
+__device__ __forceinline__ uint32_t block_sum_t0(uint32_t x, uint32_t* lds) {
+    x = wave_sum(x);
+    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = x;
+    __syncthreads();
+    uint32_t t = 0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < NW; ++i) t += lds[i];
+    __syncthreads();
+    return t;
+}
+
 __device__ __forceinline__ uint32_t utf8_len(uint32_t c) {
     return c < 0x80u ? 1u : c < 0x800u ? 2u : c < 0x10000u ? 3u : 4u;
 }

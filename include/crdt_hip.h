@@ -16,6 +16,9 @@
  *   apply_update(u)      -> crdt_hip_oplog_apply_update (replaces decode_and_add, rope.rs:222-224),
  *                           or on the device: crdt_hip_replica_apply_updates (batched)
  *   clone()              -> crdt_hip_oplog_clone (the device context is shared, never copied)
+ *   apply_update(&other) -> crdt_hip_oplog_join, or on the device crdt_hip_replica_join: the
+ *                           state-based Downstream of the Automerge adapter, doc.merge(other)
+ *                           (rope.rs:234-236), for logs that diverged
  *
  * Conventions
  *   - Every function returns int status: 0 = ok, < 0 = error (CRDT_HIP_E*).  Nothing throws or
@@ -202,6 +205,26 @@ int crdt_hip_oplog_encode_from(const crdt_hip_oplog* log, uint64_t version, uint
                                size_t cap, size_t* out_len);
 /* Decode and append an update (Downstream::apply_update / decode_and_add, rope.rs:222-224). */
 int crdt_hip_oplog_apply_update(crdt_hip_oplog* log, const uint8_t* buf, size_t len);
+/* State-based merge of two divergent logs (the reference's `Downstream for Automerge`:
+ * apply_update(&mut self, other: &Self) = doc.merge(other), rope.rs:234-236).
+ * dst <- dst U src by item identity (lamport, agent): editors that forked from a common log and
+ * both appended (each under its own agent, crdt_hip_oplog_set_agent) exchange their whole state.
+ *   - every item of src whose identity dst lacks is appended, in src's slot order (new id =
+ *     items of dst + 1 + rank among src's new items), parent and origin_right translated to dst's
+ *     ids; an item both hold becomes deleted if either has it deleted;
+ *   - *added: items appended; *tombstoned: items dst already held that the join deleted (either
+ *     may be NULL);
+ *   - validated first, and a rejected join changes nothing: CRDT_HIP_EBADLOG when two items of
+ *     one log share an identity, when an item both hold differs in codepoint or translated
+ *     parent, or when a parent does not precede its item; CRDT_HIP_ERANGE when the result would
+ *     exceed the op-log size limit; CRDT_HIP_EINVAL for a Fugue log on either side (Fugue joins
+ *     are not supported);
+ *   - joining a log with itself, or with one it already contains, changes nothing.
+ * crdt_hip_oplog_version / encode_from keep their local meaning: a joined log ships its ops to
+ * downstream replicas of that log as before (ids are the log's own); a join is not a wire update.
+ * Positional edits after a join rebuild the resolver index first, as for a loaded log. */
+int crdt_hip_oplog_join(crdt_hip_oplog* dst, const crdt_hip_oplog_view* src, uint32_t* added,
+                        uint32_t* tombstoned);
 
 /* ---- trace loader (crdt-testdata load_testing_data / chars_to_bytes, main.rs:19-23) ---------- */
 int crdt_hip_trace_load(const char* path, crdt_hip_trace** out);
@@ -334,6 +357,19 @@ int crdt_hip_updates_free(crdt_hip_updates* u);
 /* crdt_hip_replica_apply_updates with a resident batch (same semantics and validation). */
 int crdt_hip_replica_apply_resident(crdt_hip_ctx* ctx, crdt_hip_replica* r,
                                     const crdt_hip_updates* u);
+/* crdt_hip_oplog_join on the device (rope.rs:234-236): dst <- dst U src by item identity, both
+ * replicas of `ctx` (another context's: CRDT_HIP_EINVAL), with the same semantics, validation and
+ * error codes, and the same resulting log slot for slot.  Runs in HIP kernels on the context's
+ * stream; no host copy of either log is made.  The forks' common prefix (equal keys slot by slot)
+ * maps to itself; only the slots past it go through an identity hash table.  src is unchanged.
+ * After a join the next crdt_hip_replica_merge_inc of dst merges in full (*path == 0). */
+int crdt_hip_replica_join(crdt_hip_ctx* ctx, crdt_hip_replica* dst,
+                          const crdt_hip_replica* src, uint32_t* added, uint32_t* tombstoned);
+/* What the context's last crdt_hip_replica_join observed (each may be NULL): slots of the common
+ * prefix, dst slots entered into the identity table, the table's capacity, and the summed device
+ * time of the join's kernels in ns (HIP events). */
+int crdt_hip_join_stats(const crdt_hip_ctx* ctx, uint64_t* prefix_slots, uint64_t* table_slots,
+                        uint64_t* table_capacity, uint64_t* device_ns);
 /* Items held, visible codepoints (Upstream::len, rope.rs:16-19) and visible UTF-8 bytes. */
 int crdt_hip_replica_info(const crdt_hip_replica* r, uint64_t* items,
                           uint64_t* visible_codepoints, uint64_t* visible_bytes);
