@@ -261,6 +261,11 @@ int crdt_hip_set_param(crdt_hip_ctx* ctx, const char* key, uint64_t value) {
         ctx->eng.static_jumps = (uint32_t)value;
         return CRDT_HIP_OK;
     }
+    if (k == "dead_skip") {  // flag planes, codepoints of live groups only (Engine::dead_skip)
+        if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "dead_skip must be 0 or 1");
+        ctx->eng.dead_skip = (uint32_t)value;
+        return CRDT_HIP_OK;
+    }
     if (k == "doctree_k32") {  // LDS level 1 with 32-bit sibling keys (Engine::doctree_k32)
         if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "doctree_k32 must be 0 or 1");
         ctx->eng.doctree_k32 = value == 1;

@@ -17,7 +17,9 @@
 //                  tile's parent list from the parents of its non-seq items
 //    k_heads       head bitvector words, per-tile head counts
 //                  (resident RGA batches keep their jump bits with the input encoding, and
-//                  k_classify computes the heads of its tile itself: the static path, L0Args::sjump)
+//                  k_classify computes the heads of its tile itself: the static path, L0Args::sjump;
+//                  TEXT merges of such batches take k_classify_plane: the tombstone and nsq flags
+//                  from resident bit planes, the codepoints of live 16-slot groups only)
 //    k_tiles_*     exclusive scan of the per-tile (heads, weight) pairs
 //    k_runs        run records (head slot, weight prefix, key, parent run by rank lookup),
 //                  slot-order UTF-8
@@ -182,6 +184,11 @@ struct L0Args {
     // wave computes the tile's run heads (head_word) in k_heads' place.  Contracted RGA waves
     // with a list (Engine::static_wave).
     uint32_t sjump;
+    // plane path (Engine::plane_wave: a static wave merged in TEXT mode with dead_skip): the
+    // wave's range of the resident tombstone plane, 16 slots per u16 (bit = tombstoned or no
+    // character).  nsqb is then the resident nsq plane (DeviceLogs::nsq_mask), read-only in the
+    // merge: k_classify_plane takes its nsq masks there and k_runs reads it as ever.
+    const uint16_t* tomb;
 };
 
 constexpr uint32_t kTileBytes = kScanTile * 4;  // worst case: every slot a 4-byte character
@@ -610,6 +617,145 @@ __global__ __launch_bounds__(kBlock) void k_heads(L0Args a) {
         }
     }
     head_word<false>(a, wi, live, doc, nsq, vis, jw, pj);
+}
+
+// k_classify_plane: the static path of k_classify for TEXT merges of a batch that keeps its flag
+// planes (L0Args::tomb; Engine::dead_skip).  A deleted character needs nothing from its codepoint
+// word: visible = item && !tombstone and nsq = item && !previous-slot flag are both in the planes,
+// the head records need only the nsq, visible and jump words, and it weighs nothing.  So every
+// thread takes the 16-bit tombstone and nsq masks of its group from the planes (a wave reads 128
+// consecutive bytes of each) and fetches its 48 bytes of codepoint words only if the group holds a
+// visible item.  The planes carry the item mask (the tombstone plane marks every slot that holds
+// no character, the nsq plane holds items only), so the threads look no document up: only the
+// head stage's 64 lanes do, with their jump words, at the top of the kernel.  Nearly half the
+// tiles of the traces hold no visible item, and such a tile's life is its chain of dependent
+// round trips: planes (-> codepoints), with the head stage's loads beside them, not after the
+// text barrier (574 -> 434 us per launch for the two).  Dead threads do no
+// unpacking and write no text; a wave without a live thread skips both sections (the branches
+// are skipped on an empty exec mask), and a tile without one stores a weight of 0 and no text.
+// Everything k_runs and the head stage read is still written by every thread, wave and tile: visb,
+// escm (0 from a dead wave), the block scan, the list-length check and the head stage.  nsqb is
+// not written: it is the resident nsq plane, which k_runs reads in its place.
+// Multi-byte text as in k_classify, for the visible characters only: a tombstoned multi-byte
+// character raises no escape.
+__global__ __launch_bounds__(kBlock) void k_classify_plane(L0Args a) {
+    __shared__ uint32_t lds[kBlock / 64];
+    // the threads' 16-bit nsq and visible masks, which the first wave reads back as 64 words
+    __shared__ __attribute__((aligned(8))) uint16_t lnsq[kBlock];
+    __shared__ __attribute__((aligned(8))) uint16_t lvis[kBlock];
+    // (+64: one sink byte per lane for the branch-free ASCII stores below)
+    __shared__ __attribute__((aligned(16))) uint8_t sb[kTileBytes + 64];
+    const uint32_t tile = xcd_block(blockIdx.x, gridDim.x, a.xcd);
+    const uint32_t t0 = tile * kScanTile, gs = t0 + threadIdx.x * kScanItems;
+    const bool live = gs < a.nslots;
+    const uint32_t nlo = a.nsq_pre[t0 >> 6];
+    const uint32_t nhi = a.nsq_pre[min(t0 + kScanTile, a.nslots) >> 6];
+    uint32_t tb = 0xFFFFu, nq = 0;
+    if (live) {
+        tb = a.tomb[gs >> 4];
+        nq = a.nsqb[gs >> 4];
+    }
+    // the first wave's lane = a 64-slot word of the tile: its resident jump word for the head
+    // stage, loaded with the planes (a dead tile has no text copy-out to hide the load behind)
+    const uint32_t hwi = tile * (kScanTile / 64) + threadIdx.x;
+    const bool hlive = threadIdx.x < 64u && hwi * 64u < a.nslots;
+    uint64_t hjw = 0;
+    uint2 hdoc = make_uint2(0, 0);
+    if (hlive) {
+        hjw = *reinterpret_cast<const uint64_t*>(a.jbits + 2u * hwi);
+        hdoc = a.docs[a.chunk_doc[(hwi * 64u) >> a.log2m]];
+    }
+    uint4 cq[3] = {};
+    if (tb != 0xFFFFu) {  // (so live) some slot of the group holds a visible character
+        const uint4* cv = reinterpret_cast<const uint4*>(a.in_cp + 3ull * gs);  // 48 B
+#pragma unroll
+        for (int q = 0; q < 3; ++q) cq[q] = cv[q];
+    }
+    // the planes were built from the document table (k_nsq_count, k_raw_encode): the tombstone
+    // plane marks every slot that is no item and the nsq plane holds items only, so the masks
+    // need no item mask and the threads no document lookup (the head stage's lanes look theirs up)
+    const uint32_t vis = ~tb & 0xFFFFu, nsq = nq;
+    uint32_t C[16], W = 0;
+    uint64_t nib = 0;
+    if (vis) {
+        const uint32_t CW[13] = {cq[0].x, cq[0].y, cq[0].z, cq[0].w, cq[1].x, cq[1].y, cq[1].z,
+                                 cq[1].w, cq[2].x, cq[2].y, cq[2].z, cq[2].w, 0u};
+        uint32_t hi = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int byte = 3 * k, wd = byte >> 2, sh = 8 * (byte & 3);
+            const uint32_t lo = CW[wd] >> sh, up = sh > 8 ? CW[wd + 1] << (32 - sh) : 0u;
+            C[k] = (lo | up) & kCpMask;
+            hi |= (vis >> k) & 1u ? C[k] & ~0x7Fu : 0u;
+        }
+        if (hi == 0u) {
+            W = (uint32_t)__popc(vis);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const uint32_t w = (vis >> k) & 1u ? utf8_len(C[k]) : 0u;
+                W += w;
+                nib |= (uint64_t)w << (4 * k);
+            }
+        }
+    }
+    const bool esc = W != (uint32_t)__popc(vis);  // (a visible multi-byte character)
+    const uint64_t em = __ballot(esc);
+    if (live) {
+        if (esc) a.wnib[gs >> 4] = nib;
+        a.visb[gs >> 4] = (uint16_t)vis;
+        if ((threadIdx.x & 63u) == 0u) a.escm[gs >> 10] = em;  // (a wave: 1024 aligned slots)
+    }
+    lnsq[threadIdx.x] = (uint16_t)nsq;
+    lvis[threadIdx.x] = (uint16_t)vis;
+    // one scan for both: nsq items << 16 | weight (a tile holds at most 4096 and 16,384)
+    uint32_t tot;
+    const uint32_t ex = block_excl_scan<kBlock / 64>(((uint32_t)__popc(nsq) << 16) | W, lds, tot);
+    const uint32_t tw = tot & 0xFFFFu, T = tot >> 16;
+    if (vis && !esc) {
+        // every visible character of the thread is one UTF-8 byte: 16 unconditional byte stores,
+        // a slot without a visible character into the lane's sink byte
+        uint8_t* o = sb + (ex & 0xFFFFu);
+        uint8_t* sink = sb + kTileBytes + (threadIdx.x & 63u);
+        uint32_t pos = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint32_t v = (vis >> k) & 1u;
+            *(v ? o + pos : sink) = (uint8_t)C[k];
+            pos += v;
+        }
+    } else if (vis) {
+        uint8_t* o = sb + (ex & 0xFFFFu);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint32_t L = (uint32_t)(nib >> (4 * k)) & 15u, c = C[k];
+            if (L) {
+                // UTF-8: lead byte = length prefix | top bits, then 6-bit continuation bytes
+                const uint32_t s0 = 6u * (L - 1u);
+                o[0] = (uint8_t)(L == 1u ? c : (((0xFF00u >> L) & 0xFFu) | (c >> s0)));
+                if (L > 1u) o[1] = (uint8_t)(0x80u | ((c >> (s0 - 6u)) & 63u));
+                if (L > 2u) o[2] = (uint8_t)(0x80u | ((c >> (s0 - 12u)) & 63u));
+                if (L > 3u) o[3] = (uint8_t)(0x80u | (c & 63u));
+            }
+            o += L;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.tile_hw[tile].y = tw;
+    {
+        uint4* dst = reinterpret_cast<uint4*>(a.stile + (uint64_t)tile * kTileBytes);
+        const uint4* src = reinterpret_cast<const uint4*>(sb);
+        for (uint32_t i = threadIdx.x; i < (tw + 15u) / 16u; i += kBlock) dst[i] = src[i];
+    }
+    if (T != nhi - nlo && threadIdx.x == 0) atomicOr(&a.ctl[C_ERR], 1u);  // list != flags
+    // the tile's run heads, as on k_classify's static path (a tile without visible text still
+    // has heads that are live by their jump bits)
+    if (threadIdx.x < 64u) {
+        const uint64_t nw = reinterpret_cast<const uint64_t*>(lnsq)[threadIdx.x];
+        const uint64_t vw = reinterpret_cast<const uint64_t*>(lvis)[threadIdx.x];
+        const uint32_t up = (uint32_t)__shfl_up((int)(uint32_t)(hjw >> 63), 1);
+        head_word<true>(a, hwi, hlive, hdoc, nw, vw, hjw, threadIdx.x == 0u ? 1u : up);
+    }
 }
 
 // Exclusive scan of the tile {heads, weight} pairs: per-4096-tile sums, one workgroup over the
@@ -3841,10 +3987,13 @@ __device__ __forceinline__ Perm replica_perm(uint32_t kind, uint32_t n, uint64_t
 // The nsq items (items without the previous-slot flag) of every 64-slot chunk of a wave, the same
 // classification as k_classify's: 16 slots per thread (three 16-byte loads, the lanes of a wave on
 // 3 KiB of consecutive codepoint words), four lanes' 16-bit masks joined into the chunk's mask.
-__global__ __launch_bounds__(kBlock) void k_nsq_count(L0Args a, uint32_t* cnt, uint64_t* mask) {
+// With `tomb` the chunk's word of the tombstone plane too (DeviceLogs::tomb), from the same words:
+// a tombstoned item, or a slot that is no item.
+__global__ __launch_bounds__(kBlock) void k_nsq_count(L0Args a, uint32_t* cnt, uint64_t* mask,
+                                                      uint64_t* tomb) {
     const uint32_t t = blockIdx.x * kBlock + threadIdx.x;  // 16-slot group
     const uint32_t gs = t * 16u;
-    uint32_t bits = 0;
+    uint32_t bits = 0, dead = 0xFFFFu;
     if (gs < a.nslots) {
         const uint2 doc = a.docs[a.chunk_doc[gs >> a.log2m]];
         const uint32_t l0 = gs - doc.x, n = doc.y;
@@ -3859,17 +4008,24 @@ __global__ __launch_bounds__(kBlock) void k_nsq_count(L0Args a, uint32_t* cnt, u
             const uint32_t c = (lo | hi) & 0x00FFFFFFu;
             const bool it = (l0 + (uint32_t)k - 1u) < n;
             bits |= (it && !(c & kSeqBit) ? 1u : 0u) << k;
+            dead &= ~((it && !(c & kDelBit) ? 1u : 0u) << k);
         }
     }
+    // (one shuffle for both masks: nsq in the low half, tombstones in the high half)
+    bits |= dead << 16;
     // (every lane of the wave takes part in the shuffles; a chunk's four groups are lanes
     // 4i .. 4i + 3 of one wave)
     const uint32_t lane = threadIdx.x & 63u, l4 = lane & ~3u;
     const uint32_t b0 = (uint32_t)__shfl((int)bits, (int)l4), b1 = (uint32_t)__shfl((int)bits, (int)l4 + 1);
     const uint32_t b2 = (uint32_t)__shfl((int)bits, (int)l4 + 2), b3 = (uint32_t)__shfl((int)bits, (int)l4 + 3);
     if ((lane & 3u) == 0u && gs < a.nslots) {
-        const uint64_t m = (uint64_t)(b0 | (b1 << 16)) | ((uint64_t)(b2 | (b3 << 16)) << 32);
+        const uint64_t m = (uint64_t)((b0 & 0xFFFFu) | (b1 << 16)) |
+                           ((uint64_t)((b2 & 0xFFFFu) | (b3 << 16)) << 32);
         cnt[t >> 2] = (uint32_t)__popcll(m);
         mask[t >> 2] = m;
+        if (tomb)
+            tomb[t >> 2] = (uint64_t)((b0 >> 16) | (b1 & 0xFFFF0000u)) |
+                           ((uint64_t)((b2 >> 16) | (b3 & 0xFFFF0000u)) << 32);
     }
 }
 // The list itself: one workgroup per 4096-slot tile (16 slots per thread, k_classify's layout):
@@ -3980,10 +4136,11 @@ inline uint32_t ceil_log2(uint64_t x) {
 // =============================================================================================
 void DeviceLogs::release() {
     dfree(parent); dfree(key); dfree(cp);
-    dfree(nsq_par); dfree(nsq_pre); dfree(nsq_key); dfree(nsq_sums); dfree(nsq_mask); dfree(jump);
+    dfree(nsq_par); dfree(nsq_pre); dfree(nsq_key); dfree(nsq_sums); dfree(nsq_mask); dfree(tomb); dfree(jump);
     nsq_items = 0;
     nsq_ok = false;
     jump_ok = false;
+    tomb_ok = false;
     nsq_cap = nsq_pre_cap = nsq_sums_cap = jump_cap = 0;
     dfree(docs_rel); dfree(doc_rank); dfree(chunk_doc);
     dfree(raw_lam); dfree(raw_agent); dfree(raw_del); dfree(raw_cp);
@@ -4078,6 +4235,7 @@ int Engine::plan(DeviceLogs& L, const std::vector<DocInfo>& docs,
     // (a new slot layout: the compact nsq list, if any, no longer matches it)
     L.nsq_ok = false;
     L.jump_ok = false;
+    L.tomb_ok = false;
     L.nsq_items = 0;
     L.log2m = kDocAlignLog2;
     L.docs = docs;
@@ -4551,7 +4709,8 @@ int Engine::clock_mark(StageClock& c, int stage) {
     a0.in_cp = L.cp + 3ull * w.slot0;                               \
     a0.sjump = static_wave(L, w) ? 1u : 0u;                         \
     a0.jbits = a0.sjump ? L.jump + DeviceLogs::kJumpHead + (w.slot0 >> 5) : jbits_; \
-    a0.nsqb = nsqb_;                                                \
+    a0.tomb = plane_wave(L, w, ord) ? reinterpret_cast<const uint16_t*>(L.tomb + (w.slot0 >> 6)) : nullptr; \
+    a0.nsqb = a0.tomb ? reinterpret_cast<uint16_t*>(L.nsq_mask + (w.slot0 >> 6)) : nsqb_; \
     a0.wnib = wnib_;                                                \
     a0.visb = visb_;                                                \
     a0.escm = escm_;                                                \
@@ -4644,7 +4803,10 @@ int Engine::launch_level0(DeviceLogs& L, const Wave& w, bool ord, bool copy_text
     k_clear<<<std::max(1u, std::min<uint32_t>(grid_for(nq), 2048u)), 256, 0, s>>>(
         ctl_, reinterpret_cast<uint4*>(jbits_), nq, a0.sjump ? L.jump : nullptr);
     MARK(-1);
-    k_classify<<<ntiles, kBlock, 0, s>>>(a0);
+    if (a0.tomb)
+        k_classify_plane<<<ntiles, kBlock, 0, s>>>(a0);
+    else
+        k_classify<<<ntiles, kBlock, 0, s>>>(a0);
     MARK(S_CLASSIFY);
     if (!a0.sjump) k_heads<<<grid_for(w.nslots / 64), kBlock, 0, s>>>(a0);
     if (nsums == 1) {
@@ -5256,6 +5418,7 @@ int Engine::merge_async_prepare(DeviceLogs& L, AsyncMerge& m, bool timed) {
         m.eng[i]->doctree_k32 = doctree_k32;
         m.eng[i]->runs_slots = runs_slots;
         m.eng[i]->static_jumps = static_jumps;
+        m.eng[i]->dead_skip = dead_skip;
         m.eng[i]->l1_split = l1_split;
         m.eng[i]->probe_doc_ = probe_doc_;
     }
@@ -5462,6 +5625,7 @@ int Engine::merge_lanes(DeviceLogs& L, Mode mode, uint64_t* digests, uint64_t* l
         eng[i]->doctree_k32 = doctree_k32;
         eng[i]->runs_slots = runs_slots;
         eng[i]->static_jumps = static_jumps;
+        eng[i]->dead_skip = dead_skip;
         eng[i]->probe_doc_ = probe_doc_;
     }
     std::vector<int> rc(K, CRDT_HIP_OK);
@@ -5658,8 +5822,11 @@ int Engine::nsq_reserve_prefix(DeviceLogs& L) {
     if (nch + 1 > L.nsq_pre_cap) {
         dfree(L.nsq_pre);
         dfree(L.nsq_mask);
+        dfree(L.tomb);
         L.nsq_pre_cap = 0;
+        L.tomb_ok = false;
         HIPCHK(dalloc(&L.nsq_mask, nch + 1), "hipMalloc nsq masks");
+        HIPCHK(dalloc(&L.tomb, nch + 1), "hipMalloc tombstone plane");
         HIPCHK(dalloc(&L.nsq_pre, nch + 1), "hipMalloc nsq prefix");
         L.nsq_pre_cap = nch + 1;
         gen_++;  // (captured replays point at the old arrays)
@@ -5688,13 +5855,16 @@ int Engine::nsq_reserve_prefix(DeviceLogs& L) {
 // Counts of the nsq items per 64-slot chunk, scanned in place into L.nsq_pre (launches only).
 void Engine::nsq_count_scan(DeviceLogs& L) {
     const bool ord = false;  // (L0ARGS)
+    L.tomb_ok = false;       // (before L0ARGS: the launches below are not on the plane path)
     const uint32_t n = (uint32_t)(L.total_slots / 64 + 64);
     (void)hipMemsetAsync(L.nsq_pre, 0, (n + 1ull) * 4, stream);
     for (const Wave& w : L.waves) {
         L0ARGS(a0);
-        k_nsq_count<<<grid_for((w.nslots + 15) / 16), kBlock, 0, stream>>>(a0, L.nsq_pre + (w.slot0 >> 6),
-                                                                   L.nsq_mask + (w.slot0 >> 6));
+        k_nsq_count<<<grid_for((w.nslots + 15) / 16), kBlock, 0, stream>>>(
+            a0, L.nsq_pre + (w.slot0 >> 6), L.nsq_mask + (w.slot0 >> 6),
+            L.tomb ? L.tomb + (w.slot0 >> 6) : nullptr);
     }
+    L.tomb_ok = L.tomb != nullptr;
     nsq_scan(L);
 }
 void Engine::nsq_scan(DeviceLogs& L) {
@@ -5731,7 +5901,8 @@ __global__ __launch_bounds__(kBlock) void k_raw_encode(L0Args a, const uint32_t*
                                                        uint64_t* __restrict__ key,
                                                        uint8_t* __restrict__ cp3,
                                                        uint32_t* __restrict__ cnt,
-                                                       uint64_t* __restrict__ mask) {
+                                                       uint64_t* __restrict__ mask,
+                                                       uint64_t* __restrict__ tomb) {
     // four slots per lane (every column read with one vector load, the keys written as two
     // 16-byte stores); a wave = four 64-slot chunks, 16 lanes each (their nsq masks joined by
     // shuffles); the block's 1024 codepoint words are assembled in LDS and stored as 192 16-byte
@@ -5739,7 +5910,7 @@ __global__ __launch_bounds__(kBlock) void k_raw_encode(L0Args a, const uint32_t*
     __shared__ __attribute__((aligned(16))) uint32_t cb[3 * kBlock];
     const uint32_t g0 = (blockIdx.x * kBlock + threadIdx.x) * 4u;
     const uint32_t lane = threadIdx.x & 63u;
-    uint32_t nsq = 0, c[4] = {0u, 0u, 0u, 0u};
+    uint32_t nsq = 0, dead = 0xFu, c[4] = {0u, 0u, 0u, 0u};  // (dead: tombstoned or no item)
     const bool live = g0 < a.nslots;
     uint4 lm = make_uint4(0, 0, 0, 0);
     uint2 ag2 = make_uint2(0, 0);
@@ -5761,6 +5932,7 @@ __global__ __launch_bounds__(kBlock) void k_raw_encode(L0Args a, const uint32_t*
             if (l - 1u < doc.y) {
                 const bool sq = P[k] == l - 1u;
                 nsq |= (sq ? 0u : 1u) << k;
+                if (!((dl4 >> (8 * k)) & 0xFFu)) dead &= ~(1u << k);
                 c[k] = (CW[k] & 0x1FFFFFu) | ((dl4 >> (8 * k)) & 0xFFu ? kDelBit : 0u) | (sq ? kSeqBit : 0u);
             } else {
                 c[k] = cp3_get(a.in_cp, g0 + (uint32_t)k);  // (a document start or padding keeps its word)
@@ -5775,13 +5947,18 @@ __global__ __launch_bounds__(kBlock) void k_raw_encode(L0Args a, const uint32_t*
     cb[3 * threadIdx.x] = c[0] | (c[1] << 24);
     cb[3 * threadIdx.x + 1] = (c[1] >> 8) | (c[2] << 16);
     cb[3 * threadIdx.x + 2] = (c[2] >> 16) | (c[3] << 8);
-    // the chunk's mask: 16 lanes' nibbles
+    // the chunk's masks: 16 lanes' nibbles
     uint64_t m = (uint64_t)nsq << (4u * (lane & 15u));
+    uint64_t dmk = (uint64_t)dead << (4u * (lane & 15u));
 #pragma unroll
-    for (int x = 1; x < 16; x <<= 1) m |= (uint64_t)__shfl_xor((long long)m, x);
+    for (int x = 1; x < 16; x <<= 1) {
+        m |= (uint64_t)__shfl_xor((long long)m, x);
+        dmk |= (uint64_t)__shfl_xor((long long)dmk, x);
+    }
     if ((lane & 15u) == 0u && live && cnt) {
         cnt[g0 >> 6] = (uint32_t)__popcll(m);
         mask[g0 >> 6] = m;
+        if (tomb) tomb[g0 >> 6] = dmk;
     }
     __syncthreads();
     const uint32_t b0 = blockIdx.x * kBlock * 4u;
@@ -5821,14 +5998,17 @@ int Engine::raw_keep(DeviceLogs& L) {
 int Engine::raw_encode(DeviceLogs& L) {
     const bool ord = false;  // (L0ARGS)
     const bool nsq = L.nsq_ok && L.nsq_pre;
+    L.tomb_ok = false;  // (before L0ARGS: the codepoint words are rewritten below)
     if (nsq) (void)hipMemsetAsync(L.nsq_pre, 0, (L.total_slots / 64 + 65) * 4ull, stream);
     for (const Wave& w : L.waves) {
         L0ARGS(a0);
         k_raw_encode<<<grid_for((w.nslots + 3) / 4), kBlock, 0, stream>>>(
             a0, L.raw_lam + w.slot0, L.raw_agent + w.slot0, L.raw_del + w.slot0,
             L.raw_cp + w.slot0, L.key + w.slot0, L.cp + 3ull * w.slot0,
-            nsq ? L.nsq_pre + (w.slot0 >> 6) : nullptr, nsq ? L.nsq_mask + (w.slot0 >> 6) : nullptr);
+            nsq ? L.nsq_pre + (w.slot0 >> 6) : nullptr, nsq ? L.nsq_mask + (w.slot0 >> 6) : nullptr,
+            nsq && L.tomb ? L.tomb + (w.slot0 >> 6) : nullptr);
     }
+    L.tomb_ok = nsq && L.tomb;
     if (nsq) {
         nsq_scan(L);
         nsq_scatter(L);

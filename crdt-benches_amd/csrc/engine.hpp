@@ -131,7 +131,16 @@ struct DeviceLogs {
     bool nsq_ok = false;
     uint64_t nsq_cap = 0, nsq_pre_cap = 0, nsq_sums_cap = 0;
     uint32_t* nsq_sums = nullptr;  // (scan scratch)
-    uint64_t* nsq_mask = nullptr;  // (the nsq items of every 64-slot chunk, for the scatter)
+    // The flag planes (Engine::dead_skip), one u64 per 64-slot chunk each, built with the list by
+    // the pass that counts it (k_nsq_count, k_raw_encode) and valid with it (tomb_ok):
+    //  nsq_mask  bit = an item without the previous-slot flag.  The scatter reads it, and so do
+    //            the merges on the plane path: its memory is level 0's nsqb (u16 per 16 slots).
+    //  tomb      bit = a tombstoned item, or a slot that holds no character (document start,
+    //            padding): the `deleted` column as a bit column of its own.  The plane form of
+    //            k_classify fetches the codepoints of a 16-slot group only if some bit is clear.
+    uint64_t* nsq_mask = nullptr;
+    uint64_t* tomb = nullptr;
+    bool tomb_ok = false;  // the planes match the codepoint words (set with them; plan() clears it)
     // Static jump bits (Engine::static_jumps, RGA logs with a list): one allocation, word 0 the
     // sticky "bad parent" flag (a listed parent out of range, or an item that is its own parent),
     // from word kJumpHead on one bit per slot of the whole slot space, "the slot has a child that
@@ -200,6 +209,15 @@ public:
     uint32_t static_jumps = 1;
     bool static_wave(const DeviceLogs& L, const Wave& w) const {
         return static_jumps && L.nsq_ok && L.jump && L.jump_ok && !L.fugue && !w.nocon;
+    }
+    // 1: TEXT merges of waves on the static path take the plane form of k_classify
+    // (k_classify_plane): tombstones and nsq flags from the resident bit planes
+    // (DeviceLogs::tomb, nsq_mask), the codepoint words only of 16-slot groups that hold a
+    // visible item; nsqb is not written, k_runs reads the resident nsq plane.  0: k_classify
+    // reads the codepoint word of every slot.
+    uint32_t dead_skip = 1;
+    bool plane_wave(const DeviceLogs& L, const Wave& w, bool ord) const {
+        return dead_skip && !ord && static_wave(L, w) && L.tomb && L.tomb_ok;
     }
     static constexpr uint64_t kNsqReplicaSlots = 1ull << 22;
     // run contraction of RGA waves: 0 = by the wave's input (no contraction when at least

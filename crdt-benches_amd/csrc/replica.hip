@@ -758,7 +758,8 @@ int replica_replay(Engine& E, const Replica& init, const UpdateBatch& ub, Replay
                 // is not replayed)
                 (uint64_t)E.nsq_list, (uint64_t)E.contraction, (uint64_t)E.runs_slots,
                 (uint64_t)E.stile_text, (uint64_t)E.xcd_order, (uint64_t)E.text_scatter,
-                (uint64_t)E.fuse_text, (uint64_t)E.lanes, (uint64_t)E.static_jumps};
+                (uint64_t)E.fuse_text, (uint64_t)E.lanes, (uint64_t)E.static_jumps,
+                (uint64_t)E.dead_skip};
             hipStream_t s = E.stream;
             if (key != st.key || !st.exec) {
                 drop_graph(st);

@@ -161,7 +161,11 @@ const char* crdt_hip_last_error(const crdt_hip_ctx* ctx);
  * flag: 1 (default) = resident batches, and replicas of at least 2^22 slots, whose merges rebuild
  * it; 2 = every replica too; 0 = never), "static_jumps" (default 1: RGA logs with that list keep
  * their jump bits, a function of the parent column alone, with it, and the merges only read them;
- * 0 = every merge rebuilds the bits), "contraction" (run contraction of RGA waves, decided
+ * 0 = every merge rebuilds the bits), "dead_skip" (default 1: such logs also keep the tombstone
+ * and previous-slot flags as bit planes of their own, one bit per slot each, built with the list,
+ * and text merges fetch the codepoints only of 16-slot groups that hold a visible character;
+ * every merge still reads every slot's tombstone; 0 = the flags are read from the codepoint word
+ * of every slot), "contraction" (run contraction of RGA waves, decided
  * when a batch is built or logs are uploaded: 0 = by the input (default: no contraction when at
  * least 3/4 of a wave's items lack the previous-slot flag), 1 = always, 2 = never; replica
  * merges, which count no flags, contract under 0 and 1 and never under 2), "l1_group"
