@@ -290,7 +290,10 @@ class OpLog:
     def join(self, other) -> tuple:
         """State-based merge (crdt_hip_oplog_join): this log <- this log U `other` (an OpLog,
         LogArrays or LogFile) by item identity (lamport, agent).  Returns (items appended, items
-        this log held that the join tombstoned); a rejected join raises and changes nothing."""
+        this log held that the join tombstoned); a rejected join raises and changes nothing.
+        Two RGA logs or two Fugue logs: a Fugue item's side is an attribute that comes along, not
+        part of its identity.  The kind is the presence of the side column (OpLog(fugue=True),
+        LogArrays with `side`), never its contents; a mixed pair raises EINVAL."""
         v, keep = _as_view(other)
         a, t = C.c_uint32(), C.c_uint32()
         _check(lib().crdt_hip_oplog_join(self._h, C.byref(v), C.byref(a), C.byref(t)))
@@ -727,7 +730,9 @@ class Replica:
         """State-based merge on the device (crdt_hip_replica_join): this replica <- this replica U
         `other` by item identity (lamport, agent); `other` is unchanged.  Returns (items appended,
         items this replica held that the join tombstoned); a rejected join raises and changes
-        nothing."""
+        nothing.  Two RGA replicas or two Fugue replicas (made from a Fugue log or view, empty or
+        not): a Fugue item's identity is its key without the side bit, and an appended item keeps
+        its side; a mixed pair raises EINVAL."""
         a, t = C.c_uint32(), C.c_uint32()
         _check(lib().crdt_hip_replica_join(self.ctx._h, self._h, other._h, C.byref(a),
                                            C.byref(t)), self.ctx._h)
@@ -849,7 +854,8 @@ class HipMerge:
 
     def merge_from(self, other: "HipMerge") -> tuple:
         """`Downstream for Automerge`'s apply_update(&mut self, other: &Self) = doc.merge(other)
-        (rope.rs:234-236): take every op of a divergent replica (OpLog.join)."""
+        (rope.rs:234-236): take every op of a divergent replica (OpLog.join; both logs RGA or
+        both Fugue)."""
         return self.log.join(other.log)
 
 
@@ -890,7 +896,8 @@ class HipDownstream:
 
     def merge_from(self, other: "HipDownstream") -> tuple:
         """doc.merge(other) (rope.rs:234-236) on the device: both replicas decode their queued
-        updates, then this one takes every item of the other (Replica.join)."""
+        updates, then this one takes every item of the other (Replica.join; both replicas RGA or
+        both Fugue)."""
         self.flush()
         other.flush()
         return self.replica.join(other.replica)

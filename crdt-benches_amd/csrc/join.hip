@@ -5,29 +5,38 @@
 // doc.merge(other) (rope.rs:234-236): two editors that forked from a common
 // log and both appended exchange their whole state.  An item's identity is its sibling key
 // (lamport << 16 | agent), the word the replica's key column already holds; slot numbers mean
-// nothing across logs.  Same semantics as OpLog::join (oplog.cpp), slot for slot:
+// nothing across logs.  Fugue replicas (both, or neither: the kind is the replica's, set by the
+// side column of the view it was made from) join too: a left child's key carries kLeftKey
+// (bit 48) and its codepoint word kLeftBit, and the side is an attribute of the item, not part of
+// its name, so the identity is key & ~kLeftKey.  The kernels that name items take the kind as a
+// template parameter (the RGA instances mask nothing).  Same semantics as OpLog::join
+// (oplog.cpp), slot for slot:
 //   k_join_prefix  both logs, slots 1..min(n): the first slot whose keys differ (min-reduce), and
 //                  in the same pass the first slot with equal keys but another codepoint or parent.
 //                  Slots below the first difference are the forks' common prefix: they map to
 //                  themselves and never touch the table.  The host waits once here: the prefix
-//                  length sizes the tables and the reserve.
+//                  length sizes the tables and the reserve.  Whole key words are compared: a
+//                  Fugue slot that differs in the side alone ends the prefix, and the side check
+//                  behind the table rejects it.
 //   k_join_pmax    the largest key of the prefix.  Prefix slots are in no table, so an item past
 //                  the prefix is only known to be none of them when every key past the prefix (of
 //                  both logs) is above it, as it is for forks that appended local edits (lamport =
 //                  max + 1).  Otherwise the join is run again with an empty prefix.
 //   k_join_table   open-addressing table over dst's slots past the prefix: an entry is the u32
-//                  slot, claimed by atomicCAS on the empty marker, key equality by gathering
-//                  dst.key[slot]; an insert that meets its own key at another slot is a duplicate
+//                  slot, claimed by atomicCAS on the empty marker, identity equality by gathering
+//                  dst.key[slot]; an insert that meets its own identity at another slot is a
+//                  duplicate (Fugue: two keys that differ in the side bit alone are one identity)
 //   k_join_probe   one thread per src slot past the prefix: the same insert into a transient
 //                  table over src (src's own duplicates), then the lookup in dst's table:
 //                  map[s] = dst slot, or new; new items counted per block
 //   k_join_top     one workgroup: exclusive scan of the block counts, the total
 //   k_join_rank    new items: map[s] = n_dst + 1 + rank among src's new items (src's slot order)
-//   k_join_apply   <false> validates (an item both hold has the same codepoint and the same
-//                  translated parent; parents precede their items), <true> writes: appended items
-//                  get the translated parent, the key and the codepoint word with the previous-
-//                  slot flag recomputed from the translated parent and src's tombstone; items both
-//                  hold take src's tombstone.  map is injective, so one thread owns the three
+//   k_join_apply   <false> validates (an item both hold has the same codepoint, the same
+//                  translated parent and, Fugue, the same side; parents precede their items),
+//                  <true> writes: appended items get the translated parent, the key (side bit
+//                  included) and the codepoint word with the previous-slot flag recomputed from
+//                  the translated parent (a left child gets kLeftBit and never the flag, as in
+//                  k_upd_items) and src's tombstone; items both hold take src's tombstone.  map is injective, so one thread owns the three
 //                  bytes of each codepoint word it stores (byte stores, no read-modify-write of a
 //                  neighbour's bytes).  Does nothing once any check failed.
 // Every phase is a kernel of its own on the engine's stream (what one phase writes the next reads
@@ -58,7 +67,13 @@ enum JCtl { J_ERR = 0, J_FIRST,  // first slot whose keys differ (min(n) + 1: no
             J_N };
 // J_ERR bits
 constexpr uint64_t EJ_DUP_DST = 1, EJ_DUP_SRC = 2, EJ_CP = 4, EJ_PARENT = 8, EJ_CAUSAL = 16,
-                   EJ_BOUNDS = 32, EJ_TABLE = 64;
+                   EJ_BOUNDS = 32, EJ_TABLE = 64, EJ_SIDE = 128;
+
+// An item's identity in its key word: a Fugue left child's side bit is not part of its name.
+template <bool FUGUE>
+__device__ __forceinline__ uint64_t jident(uint64_t k) {
+    return FUGUE ? k & ~kLeftKey : k;
+}
 
 struct JoinArgs {
     // dst (written by k_join_apply<true> alone) and src slot arrays
@@ -149,23 +164,27 @@ __global__ __launch_bounds__(kJB) void k_join_prefix(JoinArgs a, uint32_t m) {
     ctl_min(&a.ctl[J_BADPAR], badpar == kEmpty ? ~0ull : badpar);
 }
 
+// (identities on both sides of the comparison with J_MINPOST: a left child's raw key is above
+// every right child's, whatever their lamports)
+template <bool FUGUE>
 __global__ __launch_bounds__(kJB) void k_join_pmax(JoinArgs a) {
     uint64_t mx = 0;
     for (uint64_t s = 1 + (uint64_t)blockIdx.x * kJB + threadIdx.x; s < a.P; s += (uint64_t)gridDim.x * kJB)
-        mx = max(mx, (uint64_t)a.dkey[s]);
+        mx = max(mx, jident<FUGUE>(a.dkey[s]));
     ctl_max(&a.ctl[J_PMAX], mx);
 }
 
 // Claim an entry for slot s of the log whose key column is `key`; returns the other slot that
-// already holds key k (a duplicate identity), kEmpty if none.  The table has at least twice as
+// already holds identity k (a duplicate), kEmpty if none.  The table has at least twice as
 // many entries as slots, so the probe ends; `full` reports a table that did not (never expected).
+template <bool FUGUE>
 __device__ __forceinline__ uint32_t tab_insert(uint32_t* tab, uint32_t mask, const uint64_t* key,
                                                uint32_t s, uint64_t k, bool& full) {
     uint32_t h = jhash(k) & mask;
     for (uint32_t it = 0; it <= mask; ++it) {
         const uint32_t old = atomicCAS(&tab[h], kEmpty, s);
         if (old == kEmpty) return kEmpty;
-        if (key[old] == k) return old;  // (the key column is not written by this kernel)
+        if (jident<FUGUE>(key[old]) == k) return old;  // (the key column is not written by this kernel)
         h = (h + 1u) & mask;
     }
     full = true;
@@ -173,15 +192,16 @@ __device__ __forceinline__ uint32_t tab_insert(uint32_t* tab, uint32_t mask, con
 }
 
 // dst's slots P..nd into dst's table.
+template <bool FUGUE>
 __global__ __launch_bounds__(kJB) void k_join_table(JoinArgs a) {
     uint64_t err = 0, mn = ~0ull;
     uint32_t used = 0;
     for (uint64_t s = a.P + (uint64_t)blockIdx.x * kJB + threadIdx.x; s <= a.nd; s += (uint64_t)gridDim.x * kJB) {
-        const uint64_t k = a.dkey[s];
+        const uint64_t k = jident<FUGUE>(a.dkey[s]);
         mn = min(mn, k);
         if (a.dpar[s] >= s) err |= EJ_CAUSAL;
         bool full = false;
-        if (tab_insert(a.dtab, a.dmask, a.dkey, (uint32_t)s, k, full) != kEmpty) err |= EJ_DUP_DST;
+        if (tab_insert<FUGUE>(a.dtab, a.dmask, a.dkey, (uint32_t)s, k, full) != kEmpty) err |= EJ_DUP_DST;
         else used += 1u;
         if (full) err |= EJ_TABLE;
     }
@@ -194,20 +214,21 @@ __global__ __launch_bounds__(kJB) void k_join_table(JoinArgs a) {
 
 // src's slots P..ns, block b the kJB slots from P + b kJB: src's own duplicates, the lookup in
 // dst's table (complete: k_join_table ran before), new items per block.
+template <bool FUGUE>
 __global__ __launch_bounds__(kJB) void k_join_probe(JoinArgs a) {
     const uint64_t s = (uint64_t)a.P + (uint64_t)blockIdx.x * kJB + threadIdx.x;
     uint64_t err = 0, mn = ~0ull;
     uint32_t isnew = 0;
     if (s <= a.ns) {
-        const uint64_t k = a.skey[s];
+        const uint64_t k = jident<FUGUE>(a.skey[s]);
         mn = k;
         bool full = false;
-        if (tab_insert(a.stab, a.smask, a.skey, (uint32_t)s, k, full) != kEmpty) err |= EJ_DUP_SRC;
+        if (tab_insert<FUGUE>(a.stab, a.smask, a.skey, (uint32_t)s, k, full) != kEmpty) err |= EJ_DUP_SRC;
         uint32_t d = kEmpty, h = jhash(k) & a.dmask;
         for (uint32_t it = 0; it <= a.dmask; ++it) {
             const uint32_t e = a.dtab[h];
             if (e == kEmpty) break;
-            if (a.dkey[e] == k) {
+            if (jident<FUGUE>(a.dkey[e]) == k) {
                 d = e;
                 break;
             }
@@ -254,7 +275,7 @@ __device__ __forceinline__ uint32_t jmap(const JoinArgs& a, uint32_t p) {
     return p < a.P ? p : a.map[p - a.P];
 }
 
-template <bool WRITE>
+template <bool WRITE, bool FUGUE>
 __global__ __launch_bounds__(kJB) void k_join_apply(JoinArgs a) {
     // (a key past the prefix at or below the prefix's largest: the prefix is not proven disjoint
     // from the rest, the host joins again with an empty prefix)
@@ -276,6 +297,7 @@ __global__ __launch_bounds__(kJB) void k_join_apply(JoinArgs a) {
                 }
                 if ((cs ^ cp3_get(a.dcp, d)) & kCpMaskJ) err |= EJ_CP;
                 if (jmap(a, par) != a.dpar[d]) err |= EJ_PARENT;
+                if (FUGUE && ((a.skey[s] ^ a.dkey[d]) & kLeftKey)) err |= EJ_SIDE;
             } else if (cs & kDelBit) {
                 const uint32_t cd = cp3_get(a.dcp, d);
                 if (!(cd & kDelBit)) {  // newly tombstoned
@@ -298,9 +320,12 @@ __global__ __launch_bounds__(kJB) void k_join_apply(JoinArgs a) {
         }
         const uint32_t tp = jmap(a, par);
         a.dpar[d] = tp;
-        a.dkey[d] = a.skey[s];
+        const uint64_t k = a.skey[s];
+        a.dkey[d] = k;
         // the previous-slot flag follows the translated parent: adjacency changes with the ids
-        cp3_put(a.dcp, d, (cs & (kCpMaskJ | kDelBit)) | (tp == d - 1u ? kSeqBit : 0u));
+        // (Fugue: a left child carries kLeftBit and never the flag, whatever its parent's slot)
+        const bool left = FUGUE && (k & kLeftKey);
+        cp3_put(a.dcp, d, (cs & (kCpMaskJ | kDelBit)) | (left ? kLeftBit : tp == d - 1u ? kSeqBit : 0u));
         if (!(cs & kDelBit)) {
             add_cp += 1u;
             add_b += utf8_len(cs & kCpMaskJ);
@@ -386,6 +411,7 @@ uint64_t pow2_at_least(uint64_t x) {
 
 // Everything after the prefix pass, with slots 1..P-1 taken as the common prefix.  Leaves the
 // final counters in sc.hctl (after a wait).
+template <bool FUGUE>
 int join_run(Engine& E, Replica& dst, const Replica& src, JoinScratch& sc, uint32_t P) {
     const uint32_t nd = dst.n, ns = src.n;
     hipStream_t s = E.stream;
@@ -425,15 +451,15 @@ int join_run(Engine& E, Replica& dst, const Replica& src, JoinScratch& sc, uint3
     a.ctl = sc.ctl;
     JCHK(sc.time_begin(), "join event");
     k_join_init<<<1, 64, 0, s>>>(sc.ctl, 0);
-    if (P > 1) k_join_pmax<<<grid_stride(P - 1), kJB, 0, s>>>(a);
-    if (cd) k_join_table<<<grid_stride(cd), kJB, 0, s>>>(a);
+    if (P > 1) k_join_pmax<FUGUE><<<grid_stride(P - 1), kJB, 0, s>>>(a);
+    if (cd) k_join_table<FUGUE><<<grid_stride(cd), kJB, 0, s>>>(a);
     if (cs) {
-        k_join_probe<<<nblk, kJB, 0, s>>>(a);
+        k_join_probe<FUGUE><<<nblk, kJB, 0, s>>>(a);
         k_join_top<<<1, 1024, 0, s>>>(a);
         k_join_rank<<<nblk, kJB, 0, s>>>(a);
-        k_join_apply<false><<<grid_stride(cs), kJB, 0, s>>>(a);
+        k_join_apply<false, FUGUE><<<grid_stride(cs), kJB, 0, s>>>(a);
     }
-    k_join_apply<true><<<grid_stride(ns), kJB, 0, s>>>(a);
+    k_join_apply<true, FUGUE><<<grid_stride(ns), kJB, 0, s>>>(a);
     JCHK(hipGetLastError(), "join kernels");
     JCHK(sc.time_end(), "join event");
     JCHK(hipMemcpyAsync(sc.hctl, sc.ctl, J_N * 8, hipMemcpyDeviceToHost, s), "copy join counters");
@@ -449,10 +475,12 @@ int replica_join(Engine& E, Replica& dst, const Replica& src, uint32_t* added,
     if (added) *added = 0;
     if (tombstoned) *tombstoned = 0;
     if (stats) *stats = JoinStats{};
-    if (dst.logs.fugue || src.logs.fugue) {
-        E.err = "join of a Fugue replica is not supported (RGA replicas only)";
+    // (the kind is the replica's own, whatever its items; checked before every early return)
+    if ((dst.logs.fugue != 0) != (src.logs.fugue != 0)) {
+        E.err = "join of a Fugue replica with an RGA replica: both sides must be of one kind";
         return CRDT_HIP_EINVAL;
     }
+    const bool fugue = dst.logs.fugue != 0;
     if (src.pending) {
         E.err = "replica has an unsettled decode";
         return CRDT_HIP_EINVAL;
@@ -499,13 +527,13 @@ int replica_join(Engine& E, Replica& dst, const Replica& src, uint32_t* added,
         }
     }
     // ---- table, probe, validate, write ---------------------------------------------------------
-    rc = join_run(E, dst, src, sc, P);
+    rc = fugue ? join_run<true>(E, dst, src, sc, P) : join_run<false>(E, dst, src, sc, P);
     if (rc) return rc;
     if (P > 1 && !sc.hctl[J_ERR] && sc.hctl[J_MINPOST] <= sc.hctl[J_PMAX]) {
         // some key past the prefix does not exceed every prefix key (a log that took older items
         // in an earlier join): every slot goes through the table
         P = 1;
-        rc = join_run(E, dst, src, sc, P);
+        rc = fugue ? join_run<true>(E, dst, src, sc, P) : join_run<false>(E, dst, src, sc, P);
         if (rc) return rc;
     }
     const uint64_t* c = sc.hctl;
@@ -516,6 +544,7 @@ int replica_join(Engine& E, Replica& dst, const Replica& src, uint32_t* added,
                 : e & EJ_CAUSAL  ? "join: an item's parent does not precede it"
                 : e & EJ_CP      ? "join: an item both logs hold has another codepoint in each"
                 : e & EJ_PARENT  ? "join: an item both logs hold has another parent in each"
+                : e & EJ_SIDE    ? "join: an item both logs hold has another side in each"
                 : e & EJ_TABLE   ? "join: identity table overflow"
                                  : "join writes outside the replica";
         return CRDT_HIP_EBADLOG;

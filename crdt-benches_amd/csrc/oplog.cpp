@@ -854,7 +854,7 @@ std::string OpLog::apply_update(const uint8_t* buf, size_t len) {
 
 // ---- state-based merge -------------------------------------------------------------------------
 namespace {
-// Identity (lamport << 16 | agent) -> item id, open addressing over a power of two of at least
+// Identity (lamport << 16 | agent; a Fugue item's side is no part of it) -> item id, open addressing over a power of two of at least
 // twice the items (the device join's table, join.hip, on the host).
 struct IdTable {
     std::vector<uint32_t> slot;
@@ -899,11 +899,29 @@ int OpLog::join(uint32_t ns, const uint32_t* s_parent, const uint32_t* s_oright,
                 uint32_t* tombstoned, std::string& err) {
     if (added) *added = 0;
     if (tombstoned) *tombstoned = 0;
-    if (fugue || s_side) {
-        err = "join of a Fugue log is not supported (RGA logs only)";
+    // (the kind is the presence of the side column, never its contents; checked before anything
+    // else, an empty source included)
+    if (fugue != (s_side != nullptr)) {
+        err = "join of a Fugue log with an RGA log: both sides must be of one kind";
         return CRDT_HIP_EINVAL;
     }
     const uint32_t nd = size();
+    if (fugue) {  // the rules every path that takes a caller's Fugue view applies
+        if (side.size() != nd) {
+            err = "malformed op log (side column)";
+            return CRDT_HIP_EBADLOG;
+        }
+        for (uint32_t id = 1; id <= ns; ++id) {
+            if (s_lamport[id - 1] == 0xFFFFFFFFu) {
+                err = "join: Fugue item with lamport 0xFFFFFFFF";
+                return CRDT_HIP_EBADLOG;
+            }
+            if (s_side[id - 1] && s_parent[id - 1] == 0) {
+                err = "join: an item is a left child of the document start";
+                return CRDT_HIP_EBADLOG;
+            }
+        }
+    }
     auto dkey = [&](uint32_t id) { return ((uint64_t)lamport[id - 1] << 16) | agent[id - 1]; };
     auto skey = [&](uint32_t id) { return ((uint64_t)s_lamport[id - 1] << 16) | s_agent[id - 1]; };
     // ---- validate: nothing changes before every check has passed -------------------------------
@@ -954,10 +972,15 @@ int OpLog::join(uint32_t ns, const uint32_t* s_parent, const uint32_t* s_oright,
             err = "join: an item both logs hold has another parent in each";
             return CRDT_HIP_EBADLOG;
         }
+        if (fugue && (side[d - 1] != 0) != (s_side[id - 1] != 0)) {
+            err = "join: an item both logs hold has another side in each";
+            return CRDT_HIP_EBADLOG;
+        }
         ntomb += s_deleted[id - 1] && !deleted[d - 1];
     }
     // ---- apply (src may be a view of this very log: then nothing is new and no column grows) ---
     if (nnew) reserve((size_t)nd + nnew, del_ops.size() + ntomb + ndel_new);
+    if (nnew && fugue) side.reserve((size_t)nd + nnew);
     for (uint32_t id = 1; id <= ns; ++id) {
         const uint32_t d = mp[id];
         if (d <= nd) {
@@ -972,7 +995,7 @@ int OpLog::join(uint32_t ns, const uint32_t* s_parent, const uint32_t* s_oright,
         const uint32_t o = s_oright ? s_oright[id - 1] : NIL;
         const uint8_t del = s_deleted[id - 1] ? 1 : 0;
         push_item(mp[s_parent[id - 1]], o && o <= ns ? mp[o] : o, s_lamport[id - 1],
-                  s_agent[id - 1], del, s_cp[id - 1]);
+                  s_agent[id - 1], del, s_cp[id - 1], fugue && s_side[id - 1] ? 1 : 0);
         if (del) del_ops.push_back(d);
     }
     if (added) *added = nnew;

@@ -88,18 +88,22 @@ public:
     std::vector<uint8_t> encode_from(uint64_t version) const;
     std::string apply_update(const uint8_t* buf, size_t len);
 
-    // State-based merge: this <- this U src by item identity (lamport, agent), the reference's
+    // State-based merge: this <- this U src by item identity (lamport, agent; a Fugue item's side
+    // is an attribute, not part of its name), the reference's
     // `Downstream for Automerge` apply_update(&mut self, other: &Self) = doc.merge(other)
     // (rope.rs:234-236).  Every item of src whose identity this log lacks is
     // appended in src's slot order (new id = size() + 1 + its rank among src's new items) with
     // parent and origin_right translated to this log's ids; an item both hold becomes deleted if
     // either has it deleted (newly tombstoned ids go to del_ops).  Everything is validated first
     // and a rejected join changes nothing.  Returns 0, or a CRDT_HIP_E* code with `err` set:
-    // EBADLOG (two items of one log share an identity; an item both hold differs in codepoint or
-    // translated parent; a parent that does not precede its item), ERANGE (result too large),
-    // EINVAL (a Fugue log on either side).  version() / encode_from keep their local meaning: a
-    // joined log ships its later ops to downstream replicas of that log, as before.
-    // src arrays as in crdt_hip_oplog_view (origin_right and side may be null).
+    // EBADLOG (two items of one log share an identity; an item both hold differs in codepoint,
+    // translated parent or side; a parent that does not precede its item; a Fugue src with
+    // lamport 0xFFFFFFFF or a left child of the document start), ERANGE (result too large),
+    // EINVAL (a Fugue log joined with an RGA log: the kind is the presence of the side column,
+    // s_side non-null, never its contents, and both must be of one kind).  Appended Fugue items
+    // keep their side.  version() / encode_from keep their local meaning: a joined log ships its
+    // later ops to downstream replicas of that log, as before.
+    // src arrays as in crdt_hip_oplog_view (origin_right may be null; side null: RGA).
     int join(uint32_t n, const uint32_t* s_parent, const uint32_t* s_oright,
              const uint32_t* s_lamport, const uint16_t* s_agent, const uint8_t* s_deleted,
              const uint32_t* s_cp, const uint8_t* s_side, uint32_t* added, uint32_t* tombstoned,

@@ -172,7 +172,9 @@ struct JoinStats {
 // (rope.rs:234-236).  Items of src that dst lacks are appended in src's slot
 // order with their parents translated to dst's ids; an item both hold is tombstoned if either
 // has it tombstoned.  *added: items appended; *tombstoned: items dst held that the join
-// tombstoned.  Validated first: a rejected join (EBADLOG) changes nothing.  RGA replicas only.
+// tombstoned.  Validated first: a rejected join (EBADLOG) changes nothing.  Two RGA replicas or
+// two Fugue replicas (identity = key & ~kLeftKey; an appended item keeps its side, an item both
+// hold must have the same side in each); a mixed pair is EINVAL.
 int replica_join(Engine& E, Replica& dst, const Replica& src, uint32_t* added,
                  uint32_t* tombstoned, JoinStats* stats = nullptr);
 

@@ -18,7 +18,8 @@
  *   clone()              -> crdt_hip_oplog_clone (the device context is shared, never copied)
  *   apply_update(&other) -> crdt_hip_oplog_join, or on the device crdt_hip_replica_join: the
  *                           state-based Downstream of the Automerge adapter, doc.merge(other)
- *                           (rope.rs:234-236), for logs that diverged
+ *                           (rope.rs:234-236), for logs that diverged (two RGA logs or two
+ *                           Fugue logs)
  *
  * Conventions
  *   - Every function returns int status: 0 = ok, < 0 = error (CRDT_HIP_E*).  Nothing throws or
@@ -219,14 +220,23 @@ int crdt_hip_oplog_apply_update(crdt_hip_oplog* log, const uint8_t* buf, size_t 
  *   - *added: items appended; *tombstoned: items dst already held that the join deleted (either
  *     may be NULL);
  *   - validated first, and a rejected join changes nothing: CRDT_HIP_EBADLOG when two items of
- *     one log share an identity, when an item both hold differs in codepoint or translated
- *     parent, or when a parent does not precede its item; CRDT_HIP_ERANGE when the result would
- *     exceed the op-log size limit; CRDT_HIP_EINVAL for a Fugue log on either side (Fugue joins
- *     are not supported);
+ *     one log share an identity, when an item both hold differs in codepoint, translated
+ *     parent or (Fugue) side, or when a parent does not precede its item; CRDT_HIP_ERANGE when
+ *     the result would exceed the op-log size limit;
+ *   - Fugue: two Fugue logs join like two RGA logs.  The identity stays (lamport, agent): the
+ *     side is an attribute of the item, so two items of one log that differ in side alone share
+ *     an identity, and an appended item keeps its side.  src is a caller's view, so it is also
+ *     held to the rules of crdt_hip_oplog_view (lamport 0xFFFFFFFF or a left child of the
+ *     document start: CRDT_HIP_EBADLOG).  The kind of a log is the presence of its side column
+ *     (dst set Fugue by crdt_hip_oplog_set_fugue; src->side non-NULL), never its contents, and
+ *     both must be of one kind: a Fugue log with an RGA log is CRDT_HIP_EINVAL, also when the
+ *     Fugue one has no left child or either is empty;
  *   - joining a log with itself, or with one it already contains, changes nothing.
  * crdt_hip_oplog_version / encode_from keep their local meaning: a joined log ships its ops to
  * downstream replicas of that log as before (ids are the log's own); a join is not a wire update.
- * Positional edits after a join rebuild the resolver index first, as for a loaded log. */
+ * Positional edits after a join rebuild the resolver index first, as for a loaded log (Fugue:
+ * an insert after an item that gained a right child through the join becomes a left child of
+ * that item's successor). */
 int crdt_hip_oplog_join(crdt_hip_oplog* dst, const crdt_hip_oplog_view* src, uint32_t* added,
                         uint32_t* tombstoned);
 
@@ -366,6 +376,9 @@ int crdt_hip_replica_apply_resident(crdt_hip_ctx* ctx, crdt_hip_replica* r,
  * error codes, and the same resulting log slot for slot.  Runs in HIP kernels on the context's
  * stream; no host copy of either log is made.  The forks' common prefix (equal keys slot by slot)
  * maps to itself; only the slots past it go through an identity hash table.  src is unchanged.
+ * Two RGA replicas or two Fugue replicas (crdt_hip_replica_new from a Fugue log's view, empty or
+ * not); a mixed pair is CRDT_HIP_EINVAL.  A Fugue item's identity is its key without the side
+ * bit; an appended item keeps its side, an item both hold must have the same side in each.
  * After a join the next crdt_hip_replica_merge_inc of dst merges in full (*path == 0). */
 int crdt_hip_replica_join(crdt_hip_ctx* ctx, crdt_hip_replica* dst,
                           const crdt_hip_replica* src, uint32_t* added, uint32_t* tombstoned);

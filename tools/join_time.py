@@ -6,8 +6,9 @@ made with the editing API under distinct agents.  Each repetition joins fork B i
 of fork A: wall time around the ABI call alone (the clone is made, and on the device waited for,
 outside the timed region), 1 warm-up, median of `--reps` (default 9, at least 7).  For the device
 join also the summed device time of its kernels (HIP events, crdt_hip_join_stats), the common
-prefix it found and the identity table's occupancy.  Reported, not gated: prints one JSON line
-(and writes it to --out).
+prefix it found and the identity table's occupancy.  `--order fugue` resolves
+the trace with Fugue anchors (a Fugue base, Fugue forks, Fugue replicas); everything else is the
+same.  Reported, not gated: prints one JSON line (and writes it to --out).
 """
 import argparse
 import ctypes as C
@@ -44,11 +45,13 @@ def main():
     ap.add_argument("--trace", default="automerge-paper")
     ap.add_argument("--edits", type=int, default=10000)
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--order", choices=["rga", "fugue"], default="rga")
     ap.add_argument("--out")
     args = ap.parse_args()
     reps = max(7, args.reps)
     L = crdt_hip.lib()
-    base = crdt_hip.Trace(os.path.join(ROOT, "traces", f"{args.trace}.json.gz")).resolve()
+    base = crdt_hip.Trace(os.path.join(ROOT, "traces", f"{args.trace}.json.gz")).resolve(
+        fugue=args.order == "fugue")
     a, b = fork(base, 1, 1001, args.edits), fork(base, 2, 2002, args.edits)
     na, nb, n0 = a.view().n, b.view().n, base.view().n
     added, tomb = C.c_uint32(), C.c_uint32()
@@ -80,7 +83,7 @@ def main():
         assert r.merge_digest() == want, "device join differs from the host join"
         r.close()
     out = {
-        "trace": args.trace, "edits_per_fork": args.edits, "reps": reps,
+        "trace": args.trace, "order": args.order, "edits_per_fork": args.edits, "reps": reps,
         "base_items": n0, "dst_items": na, "src_items": nb,
         "added": host_result[0], "tombstoned": host_result[1], "joined_items": host_result[2],
         "host_join_ms_median": round(statistics.median(host[1:]) * 1e3, 4),
