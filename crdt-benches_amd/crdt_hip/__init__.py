@@ -52,6 +52,9 @@ EXPORTS = [
     "crdt_hip_tree_digest", "crdt_hip_merge_len", "crdt_hip_replica_merge_len",
     "crdt_hip_replica_replay", "crdt_hip_oplog_join", "crdt_hip_replica_join",
     "crdt_hip_join_stats",
+    "crdt_hip_oplog_state_vector", "crdt_hip_oplog_encode_diff", "crdt_hip_oplog_apply_diff",
+    "crdt_hip_replica_state_vector", "crdt_hip_replica_encode_diff",
+    "crdt_hip_replica_apply_diff", "crdt_hip_delta_stats",
 ]
 
 
@@ -169,6 +172,13 @@ def lib() -> C.CDLL:
         "crdt_hip_replica_info": (i32, [vp, P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_join": (i32, [vp, vp, vp, P(u32), P(u32)]),
         "crdt_hip_join_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64)]),
+        "crdt_hip_oplog_state_vector": (i32, [vp, vp, sz, P(sz)]),
+        "crdt_hip_oplog_encode_diff": (i32, [vp, vp, sz, vp, sz, P(sz)]),
+        "crdt_hip_oplog_apply_diff": (i32, [vp, vp, sz, P(u32), P(u32)]),
+        "crdt_hip_replica_state_vector": (i32, [vp, vp, vp, sz, P(sz)]),
+        "crdt_hip_replica_encode_diff": (i32, [vp, vp, vp, sz, vp, sz, P(sz)]),
+        "crdt_hip_replica_apply_diff": (i32, [vp, vp, vp, sz, P(u32), P(u32)]),
+        "crdt_hip_delta_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge": (i32, [vp, vp, vp, sz, P(sz), P(u64)]),
         "crdt_hip_replica_merge_len": (i32, [vp, vp, P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge_inc": (i32, [vp, vp, vp, sz, P(sz), P(u64), P(u32)]),
@@ -256,6 +266,49 @@ class LogArrays:
         return LogArrays(self.parent.copy(), self.lamport.copy(), self.agent.copy(),
                          self.deleted.copy(), self.cp.copy(), self.origin_right.copy(),
                          None if self.side is None else self.side.copy())
+
+
+class SvEntry(C.Structure):
+    _fields_ = [("agent", C.c_uint32), ("lamport", C.c_uint32)]
+
+
+def _sv_pack(sv) -> tuple:
+    """[(agent, lamport)] -> (crdt_hip_sv_entry array or None, entries)."""
+    sv = list(sv)
+    if not sv:
+        return None, 0
+    arr = (SvEntry * len(sv))()
+    for i, (agent, lamport) in enumerate(sv):
+        if not (0 <= agent <= 0xFFFFFFFF and 0 <= lamport <= 0xFFFFFFFF):
+            raise CrdtHipError(-1, "state vector entry out of range")
+        arr[i].agent, arr[i].lamport = agent, lamport
+    return arr, len(sv)
+
+
+def _sv_get(call, ctx=None, guess: int = 0) -> list:
+    """call(out, cap, out_n) under the ESPACE convention -> [(agent, lamport)].  `guess`: a first
+    capacity to try (a device call scans the log every time)."""
+    n = C.c_size_t(0)
+    out, cap = ((SvEntry * guess)(), guess) if guess else (None, 0)
+    rc = call(out, cap, C.byref(n))
+    if rc == -6:
+        out = (SvEntry * n.value)()
+        rc = call(out, n.value, C.byref(n))
+    _check(rc, ctx)
+    return [(int(e.agent), int(e.lamport)) for e in out[: n.value]] if n.value else []
+
+
+def _diff_get(call, ctx=None, guess: int = 0) -> bytes:
+    """call(buf, cap, out_len) under the ESPACE convention -> the delta's bytes.  `guess`: a first
+    capacity to try (a device encode classifies the log on every call)."""
+    need = C.c_size_t(0)
+    buf, cap = (C.create_string_buffer(guess), guess) if guess else (None, 0)
+    rc = call(buf, cap, C.byref(need))
+    if rc == -6:
+        buf = C.create_string_buffer(need.value)
+        rc = call(buf, need.value, C.byref(need))
+    _check(rc, ctx)
+    return buf.raw[: need.value]
 
 
 class OpLog:
@@ -349,6 +402,25 @@ class OpLog:
 
     def apply_update(self, update: bytes) -> None:
         _check(lib().crdt_hip_oplog_apply_update(self._h, update, len(update)))
+
+    def state_vector(self) -> list:
+        """Per agent with an item, the largest lamport among its items: [(agent, lamport)] by agent
+        ascending (crdt_hip_oplog_state_vector)."""
+        return _sv_get(lambda out, cap, n: lib().crdt_hip_oplog_state_vector(self._h, out, cap, n))
+
+    def encode_diff(self, sv) -> bytes:
+        """The delta a peer with state vector `sv` lacks (crdt_hip_oplog_encode_diff): the items
+        `sv` does not cover, and the tombstones of the items it covers as identity ranges."""
+        arr, nsv = _sv_pack(sv)
+        return _diff_get(lambda buf, cap, n: lib().crdt_hip_oplog_encode_diff(
+            self._h, arr, nsv, buf, cap, n))
+
+    def apply_diff(self, data: bytes) -> tuple:
+        """this log <- this log U delta (crdt_hip_oplog_apply_diff).  Returns (items appended, items
+        this log held that became deleted); a rejected delta raises and changes nothing."""
+        a, t = C.c_uint32(), C.c_uint32()
+        _check(lib().crdt_hip_oplog_apply_diff(self._h, data, len(data), C.byref(a), C.byref(t)))
+        return int(a.value), int(t.value)
 
     def save(self, path: str) -> None:
         """Op-log file (crdt_hip_oplog_save): 64-byte-aligned SoA arrays."""
@@ -510,6 +582,15 @@ class Context:
                                          C.byref(ns)), self._h)
         return {"prefix_slots": int(p.value), "table_slots": int(t.value),
                 "table_capacity": int(c.value), "device_ns": int(ns.value)}
+
+    def delta_stats(self) -> dict:
+        """What this context's last Replica.encode_diff or apply_diff observed
+        (crdt_hip_delta_stats)."""
+        i, r, t, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().crdt_hip_delta_stats(self._h, C.byref(i), C.byref(r), C.byref(t),
+                                          C.byref(ns)), self._h)
+        return {"items": int(i.value), "ranges": int(r.value), "table_slots": int(t.value),
+                "device_ns": int(ns.value)}
 
     def merge(self, log) -> tuple:
         """Merged document: (utf8 bytes, tree digest)."""
@@ -738,6 +819,26 @@ class Replica:
                                            C.byref(t)), self.ctx._h)
         return int(a.value), int(t.value)
 
+    def state_vector(self) -> list:
+        """OpLog.state_vector on the device (crdt_hip_replica_state_vector)."""
+        return _sv_get(lambda out, cap, n: lib().crdt_hip_replica_state_vector(
+            self.ctx._h, self._h, out, cap, n), self.ctx._h, guess=256)
+
+    def encode_diff(self, sv) -> bytes:
+        """OpLog.encode_diff on the device (crdt_hip_replica_encode_diff): the same bytes; this
+        replica is unchanged."""
+        arr, nsv = _sv_pack(sv)
+        return _diff_get(lambda buf, cap, n: lib().crdt_hip_replica_encode_diff(
+            self.ctx._h, self._h, arr, nsv, buf, cap, n), self.ctx._h, guess=1 << 20)
+
+    def apply_diff(self, data: bytes) -> tuple:
+        """OpLog.apply_diff on the device (crdt_hip_replica_apply_diff): the same resulting log,
+        slot for slot; a rejected delta raises and changes nothing."""
+        a, t = C.c_uint32(), C.c_uint32()
+        _check(lib().crdt_hip_replica_apply_diff(self.ctx._h, self._h, data, len(data),
+                                                 C.byref(a), C.byref(t)), self.ctx._h)
+        return int(a.value), int(t.value)
+
     def info(self) -> tuple:
         """(items, visible codepoints, visible UTF-8 bytes)."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -858,6 +959,13 @@ class HipMerge:
         both Fugue)."""
         return self.log.join(other.log)
 
+    def sync_from(self, other: "HipMerge") -> tuple:
+        """The Yrs Downstream (rope.rs:252-255): state_vector(), the other's encode_diff against
+        it, apply_update.  Takes what this log lacks of a divergent replica without moving the
+        other's whole log.  Returns (items appended, items tombstoned, delta bytes)."""
+        delta = other.log.encode_diff(self.log.state_vector())
+        return self.log.apply_diff(delta) + (len(delta),)
+
 
 class HipDownstream:
     """`Downstream` (/root/reference/src/rope.rs:185-191) with the replica on the device.
@@ -901,6 +1009,15 @@ class HipDownstream:
         self.flush()
         other.flush()
         return self.replica.join(other.replica)
+
+    def sync_from(self, other: "HipDownstream") -> tuple:
+        """HipMerge.sync_from on the device: both replicas decode their queued updates, then this
+        one applies the other's delta against its state vector.  Returns (items appended, items
+        tombstoned, delta bytes)."""
+        self.flush()
+        other.flush()
+        delta = other.replica.encode_diff(self.replica.state_vector())
+        return self.replica.apply_diff(delta) + (len(delta),)
 
     def text(self) -> str:
         self.flush()

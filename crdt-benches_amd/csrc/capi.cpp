@@ -32,6 +32,7 @@ struct crdt_hip_ctx {
     // (initial replica, update batch), most recent first
     std::vector<std::unique_ptr<crdt::ReplayState>> replays;
     crdt::JoinStats last_join;  // what the last crdt_hip_replica_join observed
+    crdt::DeltaStats last_delta;  // what the last device encode_diff / apply_diff observed
 };
 struct crdt_hip_oplog {
     crdt::OpLog log;
@@ -875,6 +876,86 @@ int crdt_hip_join_stats(const crdt_hip_ctx* ctx, uint64_t* prefix_slots, uint64_
     if (table_slots) *table_slots = ctx->last_join.table_slots;
     if (table_capacity) *table_capacity = ctx->last_join.table_cap;
     if (device_ns) *device_ns = ctx->last_join.device_ns;
+    return 0;
+}
+// ---- state-vector delta sync ---------------------------------------------------------------------
+namespace {
+static_assert(sizeof(crdt_hip_sv_entry) == sizeof(crdt::SvEntry), "state vector entry layout");
+int sv_out(crdt_hip_ctx* ctx, const std::vector<crdt::SvEntry>& sv, crdt_hip_sv_entry* out,
+           size_t cap, size_t* out_n) {
+    *out_n = sv.size();
+    if (sv.empty()) return 0;
+    if (!out || cap < sv.size()) return set_err(ctx, CRDT_HIP_ESPACE, "buffer too small");
+    std::memcpy(out, sv.data(), sv.size() * sizeof(crdt::SvEntry));
+    return 0;
+}
+}  // namespace
+int crdt_hip_oplog_state_vector(const crdt_hip_oplog* log, crdt_hip_sv_entry* out, size_t cap,
+                                size_t* out_n) {
+    if (!log || !out_n) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    return guard(nullptr, [&] { return sv_out(nullptr, log->log.state_vector(), out, cap, out_n); });
+}
+int crdt_hip_oplog_encode_diff(const crdt_hip_oplog* log, const crdt_hip_sv_entry* sv, size_t nsv,
+                               uint8_t* buf, size_t cap, size_t* out_len) {
+    if (!log || !out_len || (!sv && nsv)) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    return guard(nullptr, [&] {
+        std::vector<uint8_t> d;
+        std::string e;
+        const int rc = log->log.encode_diff(reinterpret_cast<const crdt::SvEntry*>(sv), nsv, d, e);
+        if (rc) return set_err(nullptr, rc, e);
+        *out_len = d.size();
+        if (!buf || cap < d.size()) return set_err(nullptr, CRDT_HIP_ESPACE, "buffer too small");
+        std::memcpy(buf, d.data(), d.size());
+        return 0;
+    });
+}
+int crdt_hip_oplog_apply_diff(crdt_hip_oplog* log, const uint8_t* buf, size_t len, uint32_t* added,
+                              uint32_t* tombstoned) {
+    if (!log || (!buf && len)) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    return guard(nullptr, [&] {
+        std::string e;
+        const int rc = log->log.apply_diff(buf, len, added, tombstoned, e);
+        return rc ? set_err(nullptr, rc, e) : 0;
+    });
+}
+int crdt_hip_replica_state_vector(crdt_hip_ctx* ctx, const crdt_hip_replica* r,
+                                  crdt_hip_sv_entry* out, size_t cap, size_t* out_n) {
+    if (!ctx || !r || !out_n) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    return guard(ctx, [&] {
+        std::vector<crdt::SvEntry> sv;
+        const int rc = crdt::replica_state_vector(ctx->eng, r->r, sv);
+        if (rc) return from_engine(ctx, rc);
+        return sv_out(ctx, sv, out, cap, out_n);
+    });
+}
+int crdt_hip_replica_encode_diff(crdt_hip_ctx* ctx, const crdt_hip_replica* r,
+                                 const crdt_hip_sv_entry* sv, size_t nsv, uint8_t* buf, size_t cap,
+                                 size_t* out_len) {
+    if (!ctx || !r || !out_len || (!sv && nsv)) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    return guard(ctx, [&] {
+        return from_engine(ctx, crdt::replica_encode_diff(
+                                    ctx->eng, r->r, reinterpret_cast<const crdt::SvEntry*>(sv), nsv,
+                                    buf, cap, out_len, &ctx->last_delta));
+    });
+}
+int crdt_hip_replica_apply_diff(crdt_hip_ctx* ctx, crdt_hip_replica* r, const uint8_t* buf,
+                                size_t len, uint32_t* added, uint32_t* tombstoned) {
+    if (!ctx || !r || (!buf && len)) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    return guard(ctx, [&] {
+        return from_engine(ctx, crdt::replica_apply_diff(ctx->eng, r->r, buf, len, added, tombstoned,
+                                                         &ctx->last_delta));
+    });
+}
+int crdt_hip_delta_stats(const crdt_hip_ctx* ctx, uint64_t* items, uint64_t* ranges,
+                         uint64_t* table_slots, uint64_t* device_ns) {
+    if (!ctx) return set_err(nullptr, CRDT_HIP_EINVAL, "null context");
+    if (items) *items = ctx->last_delta.items;
+    if (ranges) *ranges = ctx->last_delta.ranges;
+    if (table_slots) *table_slots = ctx->last_delta.table_slots;
+    if (device_ns) *device_ns = ctx->last_delta.device_ns;
     return 0;
 }
 int crdt_hip_replica_info(const crdt_hip_replica* r, uint64_t* items,

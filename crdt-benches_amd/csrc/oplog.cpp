@@ -1003,4 +1003,256 @@ int OpLog::join(uint32_t ns, const uint32_t* s_parent, const uint32_t* s_oright,
     return CRDT_HIP_OK;
 }
 
+// ---- state-vector delta sync -------------------------------------------------------------------
+namespace {
+uint64_t get64(const uint8_t* p) { return (uint64_t)get32(p) | ((uint64_t)get32(p + 4) << 32); }
+void put64(std::vector<uint8_t>& b, uint64_t v) {
+    put32(b, (uint32_t)v);
+    put32(b, (uint32_t)(v >> 32));
+}
+}  // namespace
+
+int delta_frame(const uint8_t* buf, size_t len, bool fugue, uint64_t held, DeltaFrame& f,
+                std::string& err) {
+    f = DeltaFrame{};
+    if (!buf || len < 16 || get32(buf) != kDeltaMagic) {
+        err = "not a delta";
+        return CRDT_HIP_EINVAL;
+    }
+    f.version = get32(buf + 4);
+    if (f.version != kDeltaVersion && f.version != kDeltaVersionFugue) {
+        err = "unsupported delta version";
+        return CRDT_HIP_EINVAL;
+    }
+    if ((f.version == kDeltaVersionFugue) != fugue) {
+        err = fugue ? "RGA delta into a Fugue log: both sides must be of one kind"
+                    : "Fugue delta into an RGA log: both sides must be of one kind";
+        return CRDT_HIP_EINVAL;
+    }
+    f.n = get32(buf + 8);
+    f.r = get32(buf + 12);
+    f.key = 16;
+    f.pkey = f.key + 8ull * f.n;
+    f.rkey = f.pkey + 8ull * f.n;
+    f.cp = f.rkey + 8ull * f.r;
+    f.rcount = f.cp + 4ull * f.n;
+    f.bytes = f.rcount + 4ull * f.r;
+    if (f.bytes >= (1ull << 32) || (uint64_t)len != f.bytes) {
+        err = (uint64_t)len < f.bytes ? "truncated delta" : "delta size does not match its header";
+        return CRDT_HIP_EINVAL;
+    }
+    for (uint32_t k = 0; k < f.r; ++k) {
+        const uint32_t c = get32(buf + f.rcount + 4ull * k);
+        if (!c) {
+            err = "delta has an empty tombstone range";
+            return CRDT_HIP_EINVAL;
+        }
+        f.range_items += c;
+    }
+    if (f.range_items > held + f.n) {
+        err = "delta: a tombstone range names an unknown item";
+        return CRDT_HIP_EBADLOG;
+    }
+    return CRDT_HIP_OK;
+}
+
+std::vector<SvEntry> OpLog::state_vector() const {
+    std::vector<uint64_t> top(65536, 0);  // lamport + 1 (0: the agent has no item)
+    const uint32_t n = size();
+    for (uint32_t k = 0; k < n; ++k) top[agent[k]] = std::max<uint64_t>(top[agent[k]], (uint64_t)lamport[k] + 1);
+    std::vector<SvEntry> sv;
+    for (uint32_t a = 0; a < 65536; ++a)
+        if (top[a]) sv.push_back(SvEntry{a, (uint32_t)(top[a] - 1)});
+    return sv;
+}
+
+int OpLog::encode_diff(const SvEntry* sv, size_t nsv, std::vector<uint8_t>& out,
+                       std::string& err) const {
+    out.clear();
+    std::vector<uint64_t> bound(65536, 0);  // lamport + 1 (0: covers nothing of the agent)
+    for (size_t i = 0; i < nsv; ++i) {
+        if (sv[i].agent > 65535u || (i && sv[i].agent <= sv[i - 1].agent)) {
+            err = "state vector is not sorted strictly by agent, or names an agent above 65535";
+            return CRDT_HIP_EINVAL;
+        }
+        bound[sv[i].agent] = (uint64_t)sv[i].lamport + 1;
+    }
+    const uint32_t n = size();
+    auto key = [&](uint32_t k) { return ((uint64_t)lamport[k] << 16) | agent[k]; };
+    auto covered = [&](uint32_t k) { return (uint64_t)lamport[k] < bound[agent[k]]; };
+    std::vector<uint32_t> items, heads, counts;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (!covered(k)) {
+            items.push_back(k);
+            continue;
+        }
+        if (!deleted[k]) continue;
+        // (a covered tombstone extends the range of the slot before it, or begins one)
+        if (k && covered(k - 1) && deleted[k - 1] && key(k) == key(k - 1) + (1ull << 16)) counts.back()++;
+        else {
+            heads.push_back(k);
+            counts.push_back(1);
+        }
+    }
+    const uint64_t bytes = 16 + 20ull * items.size() + 12ull * heads.size();
+    if (bytes >= (1ull << 32)) {
+        err = "delta too large";
+        return CRDT_HIP_ERANGE;
+    }
+    out.reserve(bytes);
+    put32(out, kDeltaMagic);
+    put32(out, fugue ? kDeltaVersionFugue : kDeltaVersion);
+    put32(out, (uint32_t)items.size());
+    put32(out, (uint32_t)heads.size());
+    for (uint32_t k : items) put64(out, key(k));
+    for (uint32_t k : items) put64(out, parent[k] ? key(parent[k] - 1) : kDeltaStart);
+    for (uint32_t k : heads) put64(out, key(k));
+    for (uint32_t k : items)
+        put32(out, (cp[k] & kDeltaCpMask) | (deleted[k] ? kDeltaTombBit : 0u) |
+                       (fugue && side[k] ? kDeltaSideBit : 0u));
+    for (uint32_t c : counts) put32(out, c);
+    return CRDT_HIP_OK;
+}
+
+int OpLog::apply_diff(const uint8_t* buf, size_t len, uint32_t* added, uint32_t* tombstoned,
+                      std::string& err) {
+    if (added) *added = 0;
+    if (tombstoned) *tombstoned = 0;
+    const uint32_t nd = size();
+    DeltaFrame f;
+    int rc = delta_frame(buf, len, fugue, nd, f, err);
+    if (rc) return rc;
+    if (fugue && side.size() != nd) {
+        err = "malformed op log (side column)";
+        return CRDT_HIP_EBADLOG;
+    }
+    const uint32_t n = f.n;
+    auto K = [&](uint32_t i) { return get64(buf + f.key + 8ull * i); };      // delta item i (0-based)
+    auto PK = [&](uint32_t i) { return get64(buf + f.pkey + 8ull * i); };
+    auto CP = [&](uint32_t i) { return get32(buf + f.cp + 4ull * i); };
+    auto dkey = [&](uint32_t id) { return ((uint64_t)lamport[id - 1] << 16) | agent[id - 1]; };
+    auto ikey = [&](uint32_t e) { return K(e - 1); };  // (table entries are 1-based)
+    const uint32_t reserved = ~(kDeltaCpMask | kDeltaTombBit | (fugue ? kDeltaSideBit : 0u));
+    // ---- validate: nothing changes before every check has passed -------------------------------
+    IdTable dt(nd), it(n);
+    for (uint32_t id = 1; id <= nd; ++id)
+        if (dt.insert(dkey(id), id, dkey)) {
+            err = "delta: two items of the log share an identity (lamport, agent)";
+            return CRDT_HIP_EBADLOG;
+        }
+    // delta item -> id in this log (new items: nd + 1 + rank in the delta's order), and the
+    // translated parent of a new item
+    std::vector<uint32_t> mp(n), tpar(n);
+    uint32_t nnew = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t k = K(i);
+        const uint32_t c = CP(i);
+        if (k >= kDeltaKeyEnd || (c & reserved)) {
+            err = "delta: malformed item";
+            return CRDT_HIP_EBADLOG;
+        }
+        if (it.insert(k, i + 1, ikey)) {
+            err = "delta: two items share an identity (lamport, agent)";
+            return CRDT_HIP_EBADLOG;
+        }
+        const uint64_t pk = PK(i);
+        const uint32_t d = dt.find(k, dkey);
+        if (d) {  // the log holds the item
+            mp[i] = d;
+            const uint32_t p = parent[d - 1];
+            if ((cp[d - 1] ^ c) & kDeltaCpMask) {
+                err = "delta: an item both hold has another codepoint in each";
+                return CRDT_HIP_EBADLOG;
+            }
+            if ((p ? dkey(p) : kDeltaStart) != pk) {
+                err = "delta: an item both hold has another parent in each";
+                return CRDT_HIP_EBADLOG;
+            }
+            if (fugue && (side[d - 1] != 0) != ((c & kDeltaSideBit) != 0)) {
+                err = "delta: an item both hold has another side in each";
+                return CRDT_HIP_EBADLOG;
+            }
+            continue;
+        }
+        mp[i] = nd + 1u + nnew++;
+        if (fugue) {
+            if ((k >> 16) == 0xFFFFFFFFull) {
+                err = "delta: Fugue item with lamport 0xFFFFFFFF";
+                return CRDT_HIP_EBADLOG;
+            }
+            if ((c & kDeltaSideBit) && pk == kDeltaStart) {
+                err = "delta: an item is a left child of the document start";
+                return CRDT_HIP_EBADLOG;
+            }
+        }
+        if (pk == kDeltaStart) {
+            tpar[i] = 0;
+            continue;
+        }
+        uint32_t p = pk < kDeltaKeyEnd ? dt.find(pk, dkey) : 0u;
+        if (!p && pk < kDeltaKeyEnd) {
+            const uint32_t e = it.find(pk, ikey);  // (an earlier item of the delta, new like this one)
+            if (e && e - 1 < i) p = mp[e - 1];
+        }
+        if (!p) {
+            err = "delta: an item's parent is unknown or does not precede it";
+            return CRDT_HIP_EBADLOG;
+        }
+        tpar[i] = p;
+    }
+    if ((uint64_t)nd + nnew >= 0x7FFFFFF0ull) {
+        err = "op log too large";
+        return CRDT_HIP_ERANGE;
+    }
+    // every identity of every range, after the items
+    std::vector<uint32_t> rid;
+    rid.reserve(f.range_items);
+    for (uint32_t q = 0; q < f.r; ++q) {
+        const uint64_t k0 = get64(buf + f.rkey + 8ull * q);
+        const uint32_t cnt = get32(buf + f.rcount + 4ull * q);
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const uint64_t k = k0 + ((uint64_t)j << 16);
+            uint32_t d = 0;
+            if (k0 < kDeltaKeyEnd && k < kDeltaKeyEnd) {
+                d = dt.find(k, dkey);
+                if (!d) {
+                    const uint32_t e = it.find(k, ikey);
+                    if (e) d = mp[e - 1];
+                }
+            }
+            if (!d) {
+                err = "delta: a tombstone range names an unknown item";
+                return CRDT_HIP_EBADLOG;
+            }
+            rid.push_back(d);
+        }
+    }
+    // ---- apply ---------------------------------------------------------------------------------
+    if (nnew) reserve((size_t)nd + nnew, del_ops.size() + n + rid.size());
+    if (nnew && fugue) side.reserve((size_t)nd + nnew);
+    uint32_t ntomb = 0;
+    auto kill = [&](uint32_t d) {  // (an item appended by this delta counts as added, not tombstoned)
+        if (deleted[d - 1]) return;
+        del_ops.push_back(d);
+        mark_deleted(d);
+        ntomb += d <= nd;
+    };
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t c = CP(i), d = mp[i];
+        if (d <= nd) {
+            if (c & kDeltaTombBit) kill(d);
+            continue;
+        }
+        const uint64_t k = K(i);
+        const uint8_t del = (c & kDeltaTombBit) ? 1 : 0;
+        push_item(tpar[i], NIL, (uint32_t)(k >> 16), (uint16_t)k, del, c & kDeltaCpMask,
+                  fugue && (c & kDeltaSideBit) ? 1 : 0);
+        if (del) del_ops.push_back(d);
+    }
+    for (uint32_t d : rid) kill(d);
+    if (added) *added = nnew;
+    if (tombstoned) *tombstoned = ntomb;
+    return CRDT_HIP_OK;
+}
+
 }  // namespace crdt

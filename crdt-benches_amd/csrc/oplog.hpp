@@ -51,6 +51,35 @@ constexpr uint32_t kUpdateVersion = 1;
 constexpr uint32_t kUpdateVersionFugue = 2;
 constexpr uint32_t kUpdateSideBit = 0x80000000u;
 
+// Delta wire format (OpLog::encode_diff / apply_diff, and the kernels of delta.hip), little-endian:
+//   header  4 x u32: kDeltaMagic, version (1 RGA, 2 Fugue), n items, r tombstone ranges
+//   key[n]  u64  identity lamport << 16 | agent          pkey[n] u64  the parent's identity
+//   rkey[r] u64  identity of a range's first item        (kDeltaStart: the document start)
+//   cp[n]   u32  bits 0-20 codepoint, bit 30 tombstone, bit 31 side (version 2 only)
+//   rcount[r] u32  items of the range (>= 1): identities rkey, rkey + (1 << 16), ...
+// 16 + 20 n + 12 r bytes, below 4 GiB.  Items are named by identity: slot numbers mean nothing
+// across logs.
+constexpr uint32_t kDeltaMagic = 0x44445243u;  // "CRDD"
+constexpr uint32_t kDeltaVersion = 1, kDeltaVersionFugue = 2;
+constexpr uint64_t kDeltaStart = ~0ull;
+constexpr uint32_t kDeltaCpMask = 0x001FFFFFu, kDeltaTombBit = 0x40000000u, kDeltaSideBit = 0x80000000u;
+constexpr uint64_t kDeltaKeyEnd = 1ull << 48;  // identities are below it
+struct SvEntry {
+    uint32_t agent, lamport;
+};
+// The columns of a delta inside its buffer (byte offsets from its start).
+struct DeltaFrame {
+    uint32_t version = 0, n = 0, r = 0;
+    uint64_t key = 0, pkey = 0, rkey = 0, cp = 0, rcount = 0, bytes = 0;
+    uint64_t range_items = 0;  // sum of the range counts
+};
+// The checks of apply_diff that need no log, shared by the host and the device path: magic,
+// version against the log's kind, the exact size, no range count of 0 (CRDT_HIP_EINVAL); ranges
+// that name more identities than the log and the delta together can hold name an unknown one
+// (CRDT_HIP_EBADLOG).  `held`: items of the destination.
+int delta_frame(const uint8_t* buf, size_t len, bool fugue, uint64_t held, DeltaFrame& f,
+                std::string& err);
+
 class OpLog {
 public:
     // ---- SoA (index k holds item id k+1) ----
@@ -108,6 +137,18 @@ public:
              const uint32_t* s_lamport, const uint16_t* s_agent, const uint8_t* s_deleted,
              const uint32_t* s_cp, const uint8_t* s_side, uint32_t* added, uint32_t* tombstoned,
              std::string& err);
+
+    // State-vector delta sync (crdt_hip.h, "delta sync"): what a peer lacks, by item identity.
+    // state_vector: per agent with an item its largest lamport, by agent ascending.
+    // encode_diff: the delta against a peer's vector (wire layout at kDeltaMagic), CRDT_HIP_EINVAL
+    // for a vector not strictly sorted by agent or with an agent above 65535, ERANGE for a delta
+    // of 4 GiB or more.  apply_diff: this <- this U delta, validated first (a rejected delta
+    // changes nothing); appended items get origin_right = NIL, newly tombstoned ids go to del_ops
+    // and the positional index is marked stale, as by join.
+    std::vector<SvEntry> state_vector() const;
+    int encode_diff(const SvEntry* sv, size_t nsv, std::vector<uint8_t>& out, std::string& err) const;
+    int apply_diff(const uint8_t* buf, size_t len, uint32_t* added, uint32_t* tombstoned,
+                   std::string& err);
 
     // Append a fully-specified item (synthetic generators / decoding); marks the positional
     // index stale.

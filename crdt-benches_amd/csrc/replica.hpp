@@ -178,6 +178,28 @@ struct JoinStats {
 int replica_join(Engine& E, Replica& dst, const Replica& src, uint32_t* added,
                  uint32_t* tombstoned, JoinStats* stats = nullptr);
 
+// State-vector delta sync (delta.hip; wire layout and host twin in oplog.hpp / oplog.cpp): the
+// reference's Yrs Downstream state_vector() + encode_diff_v1(&sv) + apply_update
+// (rope.rs:252-255, :265-268) for replicas that diverged.  Same bytes and same resulting log as
+// OpLog::state_vector / encode_diff / apply_diff.
+struct DeltaStats {  // what the last device encode or apply observed (crdt_hip_delta_stats)
+    uint64_t items = 0;        // items of the delta
+    uint64_t ranges = 0;       // tombstone ranges of the delta
+    uint64_t table_slots = 0;  // apply: dst slots entered into the identity table (all of them)
+    uint64_t device_ns = 0;    // summed device time of the call's kernels (HIP events)
+};
+struct SvEntry;
+// Per agent with an item, its largest lamport, by agent ascending.
+int replica_state_vector(Engine& E, const Replica& r, std::vector<SvEntry>& out,
+                         DeltaStats* stats = nullptr);
+// The items of r that `sv` does not cover, in slot order, and the tombstones of the items it
+// covers as identity ranges.  *out_len: the delta's size; ESPACE when buf is null or cap short.
+int replica_encode_diff(Engine& E, const Replica& r, const SvEntry* sv, size_t nsv, uint8_t* buf,
+                        size_t cap, size_t* out_len, DeltaStats* stats = nullptr);
+// dst <- dst U delta, validated first: a rejected delta (EINVAL, EBADLOG, ERANGE) changes nothing.
+int replica_apply_diff(Engine& E, Replica& dst, const uint8_t* buf, size_t len, uint32_t* added,
+                       uint32_t* tombstoned, DeltaStats* stats = nullptr);
+
 // Incremental merge (incr.hip): the merged text (may be null), its UTF-8 bytes and codepoints;
 // *path = 1 when only the items appended since the previous merge_inc were ranked, 0 for a
 // full merge (the first call, a concurrent update, more than kIncMax new items, Fugue).

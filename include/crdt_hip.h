@@ -20,6 +20,10 @@
  *                           state-based Downstream of the Automerge adapter, doc.merge(other)
  *                           (rope.rs:234-236), for logs that diverged (two RGA logs or two
  *                           Fugue logs)
+ *   state_vector / encode_diff_v1 / apply_update (the Yrs adapter, rope.rs:252-255)
+ *                        -> crdt_hip_oplog_state_vector / _encode_diff / _apply_diff, or on the
+ *                           device crdt_hip_replica_state_vector / _encode_diff / _apply_diff:
+ *                           divergent logs exchange only what the other lacks ("delta sync")
  *
  * Conventions
  *   - Every function returns int status: 0 = ok, < 0 = error (CRDT_HIP_E*).  Nothing throws or
@@ -240,6 +244,74 @@ int crdt_hip_oplog_apply_update(crdt_hip_oplog* log, const uint8_t* buf, size_t 
 int crdt_hip_oplog_join(crdt_hip_oplog* dst, const crdt_hip_oplog_view* src, uint32_t* added,
                         uint32_t* tombstoned);
 
+/* ---- delta sync: exchange only what the peer lacks ------------------------------------------
+ * The Downstream of the reference's Yrs adapter (rope.rs:252-255, :265-268: state_vector() +
+ * encode_diff_v1(&sv) + apply_update) for two logs that diverged.  A join ships the other side's
+ * whole log; here the receiver sends its state vector, the sender answers with a delta, and the
+ * receiver applies it:  dst.apply_diff(src.encode_diff(dst.state_vector())).
+ *
+ * State vector: for every agent that has at least one item, the largest lamport among its items,
+ * sorted by agent ascending.  An item is covered by a vector when its agent has an entry and its
+ * lamport is <= that entry's (an agent whose only item has lamport 0 still has an entry; an
+ * empty vector covers nothing).
+ *
+ * Delta (little-endian; n items, r tombstone ranges; 16 + 20 n + 12 r bytes, below 4 GiB):
+ *   header    4 x u32: magic 0x44445243 ("CRDD"), version (1 RGA, 2 Fugue), n, r
+ *   key[n]    u64  identity lamport << 16 | agent
+ *   pkey[n]   u64  the parent's identity, 0xFFFFFFFFFFFFFFFF for the document start
+ *   rkey[r]   u64  identity of a range's first item
+ *   cp[n]     u32  bits 0-20 codepoint, bit 30 tombstone, bit 31 side (version 2 only)
+ *   rcount[r] u32  items of the range, >= 1
+ * Items: every item the vector does not cover, in the log's slot order; parents are named by
+ * identity because slot numbers mean nothing across logs.  Ranges: every tombstoned item the
+ * vector covers (the peer holds it and may not know it is deleted), as maximal runs of consecutive
+ * slots that are all tombstoned and covered and whose identities ascend by 1 << 16 (one agent,
+ * consecutive lamports; a Fugue item's identity has no side bit).  origin_right is not carried
+ * (no merge reads it): appended items get origin_right = NIL, as in a join from a view without
+ * that column.
+ *
+ * Apply: dst <- dst U delta, validated first; a rejected delta changes nothing.  A delta item dst
+ * lacks is appended in the delta's order (new id = items of dst + 1 + rank among the new items),
+ * its parent looked up by identity in dst or among earlier delta items, side and tombstone kept;
+ * one dst holds (a stale vector, a delta sent twice) must agree in codepoint, parent identity and
+ * side, and its tombstone is OR-ed in; every identity of every range must be known to dst after
+ * the items, and those items become tombstoned.  *added / *tombstoned as for the join (either may
+ * be NULL); the same delta applied again gives (0, 0).
+ *   CRDT_HIP_EINVAL  bad magic or version; a buffer shorter or longer than its header says; a
+ *                    range count of 0; a version-2 delta into an RGA log or replica, or version 1
+ *                    into a Fugue one (the kind is the presence of the side column, as for a join)
+ *   CRDT_HIP_EBADLOG two delta items share an identity; an identity of 2^48 or more, or reserved
+ *                    bits set in a cp word; a parent identity that is unknown or does not precede
+ *                    its item in the delta; an item both hold that differs in codepoint, parent or
+ *                    side; a range that names an unknown identity (ranges that together name more
+ *                    items than dst and the delta hold do); Fugue: lamport 0xFFFFFFFF or a left
+ *                    child of the document start
+ *   CRDT_HIP_ERANGE  the result would exceed the op-log size limit
+ *
+ * Precondition: dst.apply_diff(src.encode_diff(dst.state_vector())) leaves dst equal, slot for
+ * slot, to dst joined with src (origin_right absent) whenever both logs are per-agent
+ * prefix-closed: each holds every item of an agent up to the largest lamport it holds of that
+ * agent.  Every log built from local edits, wire updates, joins and deltas is.  A violation that
+ * can be seen (a parent that is missing, a range over an unknown item) is CRDT_HIP_EBADLOG with
+ * nothing changed; one that cannot (a gap below the vector's entry that no delta item refers to)
+ * leaves the gap.
+ *
+ * Output buffers follow crdt_hip_oplog_encode_from: a NULL or short buffer sets *out_len / *out_n
+ * to the need and returns CRDT_HIP_ESPACE.  A vector that is not sorted strictly by agent, or has
+ * an agent above 65535, is CRDT_HIP_EINVAL.  The host and the device calls produce the same bytes
+ * and the same resulting log.  The host apply marks the resolver index stale and appends newly
+ * tombstoned ids to the log's delete ops, as crdt_hip_oplog_join does. */
+typedef struct {
+    uint32_t agent;
+    uint32_t lamport;
+} crdt_hip_sv_entry;
+int crdt_hip_oplog_state_vector(const crdt_hip_oplog* log, crdt_hip_sv_entry* out, size_t cap,
+                                size_t* out_n);
+int crdt_hip_oplog_encode_diff(const crdt_hip_oplog* log, const crdt_hip_sv_entry* sv, size_t nsv,
+                               uint8_t* buf, size_t cap, size_t* out_len);
+int crdt_hip_oplog_apply_diff(crdt_hip_oplog* log, const uint8_t* buf, size_t len,
+                              uint32_t* added, uint32_t* tombstoned);
+
 /* ---- trace loader (crdt-testdata load_testing_data / chars_to_bytes, main.rs:19-23) ---------- */
 int crdt_hip_trace_load(const char* path, crdt_hip_trace** out);
 void crdt_hip_trace_free(crdt_hip_trace* t);
@@ -387,6 +459,26 @@ int crdt_hip_replica_join(crdt_hip_ctx* ctx, crdt_hip_replica* dst,
  * time of the join's kernels in ns (HIP events). */
 int crdt_hip_join_stats(const crdt_hip_ctx* ctx, uint64_t* prefix_slots, uint64_t* table_slots,
                         uint64_t* table_capacity, uint64_t* device_ns);
+/* Delta sync on the device (see "delta sync" above): crdt_hip_oplog_state_vector / encode_diff /
+ * apply_diff for a replica of `ctx` (another context's: CRDT_HIP_EINVAL), with the same bytes,
+ * the same validation and error codes and the same resulting log slot for slot.  HIP kernels on
+ * the context's stream; no host copy of the replica's columns is made (encode_diff waits once for
+ * the delta's size, then copies its bytes; apply_diff uploads the bytes and waits once).  An apply
+ * builds an identity table over every item of dst, so its device work is O(items of dst) however
+ * small the delta: what a delta saves is the bytes exchanged.  After an apply_diff the next
+ * crdt_hip_replica_merge_inc merges in full (*path == 0), as after a join. */
+int crdt_hip_replica_state_vector(crdt_hip_ctx* ctx, const crdt_hip_replica* r,
+                                  crdt_hip_sv_entry* out, size_t cap, size_t* out_n);
+int crdt_hip_replica_encode_diff(crdt_hip_ctx* ctx, const crdt_hip_replica* r,
+                                 const crdt_hip_sv_entry* sv, size_t nsv, uint8_t* buf, size_t cap,
+                                 size_t* out_len);
+int crdt_hip_replica_apply_diff(crdt_hip_ctx* ctx, crdt_hip_replica* r, const uint8_t* buf,
+                                size_t len, uint32_t* added, uint32_t* tombstoned);
+/* What the context's last device encode_diff or apply_diff observed (each may be NULL): items and
+ * tombstone ranges of the delta, dst slots entered into the identity table (apply; 0 for an
+ * encode), and the summed device time of the call's kernels in ns (HIP events). */
+int crdt_hip_delta_stats(const crdt_hip_ctx* ctx, uint64_t* items, uint64_t* ranges,
+                         uint64_t* table_slots, uint64_t* device_ns);
 /* Items held, visible codepoints (Upstream::len, rope.rs:16-19) and visible UTF-8 bytes. */
 int crdt_hip_replica_info(const crdt_hip_replica* r, uint64_t* items,
                           uint64_t* visible_codepoints, uint64_t* visible_bytes);
