@@ -55,6 +55,8 @@ EXPORTS = [
     "crdt_hip_oplog_state_vector", "crdt_hip_oplog_encode_diff", "crdt_hip_oplog_apply_diff",
     "crdt_hip_replica_state_vector", "crdt_hip_replica_encode_diff",
     "crdt_hip_replica_apply_diff", "crdt_hip_delta_stats",
+    "crdt_hip_oplog_mark", "crdt_hip_mark_free", "crdt_hip_oplog_patches_since",
+    "crdt_hip_replica_mark", "crdt_hip_replica_patches_since", "crdt_hip_patch_stats",
 ]
 
 
@@ -179,6 +181,12 @@ def lib() -> C.CDLL:
         "crdt_hip_replica_encode_diff": (i32, [vp, vp, vp, sz, vp, sz, P(sz)]),
         "crdt_hip_replica_apply_diff": (i32, [vp, vp, vp, sz, P(u32), P(u32)]),
         "crdt_hip_delta_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64)]),
+        "crdt_hip_oplog_mark": (i32, [vp, P(vp)]),
+        "crdt_hip_mark_free": (None, [vp]),
+        "crdt_hip_oplog_patches_since": (i32, [vp, vp, vp, sz, P(sz), vp, sz, P(sz)]),
+        "crdt_hip_replica_mark": (i32, [vp, vp, P(vp)]),
+        "crdt_hip_replica_patches_since": (i32, [vp, vp, vp, vp, sz, P(sz), vp, sz, P(sz)]),
+        "crdt_hip_patch_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge": (i32, [vp, vp, vp, sz, P(sz), P(u64)]),
         "crdt_hip_replica_merge_len": (i32, [vp, vp, P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge_inc": (i32, [vp, vp, vp, sz, P(sz), P(u64), P(u32)]),
@@ -311,6 +319,60 @@ def _diff_get(call, ctx=None, guess: int = 0) -> bytes:
     return buf.raw[: need.value]
 
 
+class Patch(C.Structure):
+    """crdt_hip_patch: replace(pos..pos + del, ins[ins_off, ins_off + ins_len))."""
+    _fields_ = [("pos", C.c_uint64), ("ins_off", C.c_uint64), ("dele", C.c_uint32),
+                ("ins_len", C.c_uint32)]
+
+
+class Mark:
+    """A version of one OpLog or one Replica (crdt_hip_mark), taken by their mark() and passed to
+    their patches_since().  It belongs to the object it was taken from (a clone is another owner),
+    stays valid across that object's later edits, updates, joins and deltas, and keeps its owner
+    alive."""
+
+    def __init__(self, handle, owner):
+        self._h = handle
+        self.owner = owner
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and _LIB is not None:
+            _LIB.crdt_hip_mark_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def _patches_get(call, ctx=None, guess: tuple = (0, 0)) -> tuple:
+    """call(out, cap, out_n, ins, ins_cap, out_ins) under the ESPACE convention -> (the
+    crdt_hip_patch array as a structured numpy array, the `ins` bytes).  `guess`: first capacities
+    to try (a device call streams the replica's document order every time)."""
+    n, nb = C.c_size_t(0), C.c_size_t(0)
+    out = np.zeros(guess[0], PATCH_DTYPE)
+    ins = np.zeros(guess[1], np.uint8)
+    rc = call(out.ctypes.data if out.size else None, out.size, C.byref(n),
+              ins.ctypes.data if ins.size else None, ins.size, C.byref(nb))
+    if rc == -6:
+        out = np.zeros(n.value, PATCH_DTYPE)
+        ins = np.zeros(nb.value, np.uint8)
+        rc = call(out.ctypes.data if out.size else None, out.size, C.byref(n),
+                  ins.ctypes.data if ins.size else None, ins.size, C.byref(nb))
+    _check(rc, ctx)
+    return out[: n.value], ins[: nb.value].tobytes()
+
+
+PATCH_DTYPE = np.dtype([("pos", "<u8"), ("ins_off", "<u8"), ("del", "<u4"), ("ins_len", "<u4")])
+assert PATCH_DTYPE.itemsize == C.sizeof(Patch) == 24
+
+
+def _patch_list(raw: tuple) -> list:
+    """(crdt_hip_patch array, ins bytes) -> [(pos, del, ins: str)]."""
+    arr, ins = raw
+    return [(int(p["pos"]), int(p["del"]),
+             ins[int(p["ins_off"]): int(p["ins_off"]) + int(p["ins_len"])].decode("utf-8"))
+            for p in arr]
+
+
 class OpLog:
     """Host-side resolver (positional patches -> anchor op log), crdt_hip_oplog_*."""
 
@@ -421,6 +483,23 @@ class OpLog:
         a, t = C.c_uint32(), C.c_uint32()
         _check(lib().crdt_hip_oplog_apply_diff(self._h, data, len(data), C.byref(a), C.byref(t)))
         return int(a.value), int(t.value)
+
+    def mark(self) -> Mark:
+        """Remember this version of the log (crdt_hip_oplog_mark)."""
+        h = C.c_void_p()
+        _check(lib().crdt_hip_oplog_mark(self._h, C.byref(h)))
+        return Mark(h, self)
+
+    def patches_since_raw(self, mark: Mark) -> tuple:
+        """(crdt_hip_patch array as a structured numpy array, `ins` bytes) of
+        crdt_hip_oplog_patches_since."""
+        return _patches_get(lambda *a: lib().crdt_hip_oplog_patches_since(self._h, mark._h, *a))
+
+    def patches_since(self, mark: Mark) -> list:
+        """What changed in the document since `mark`, as [(pos, del, ins: str)] ascending in pos:
+        applied in that order, each as replace(pos, pos + del, ins), to the text at the mark they
+        give the text now (crdt_hip_oplog_patches_since)."""
+        return _patch_list(self.patches_since_raw(mark))
 
     def save(self, path: str) -> None:
         """Op-log file (crdt_hip_oplog_save): 64-byte-aligned SoA arrays."""
@@ -590,6 +669,14 @@ class Context:
         _check(lib().crdt_hip_delta_stats(self._h, C.byref(i), C.byref(r), C.byref(t),
                                           C.byref(ns)), self._h)
         return {"items": int(i.value), "ranges": int(r.value), "table_slots": int(t.value),
+                "device_ns": int(ns.value)}
+
+    def patch_stats(self) -> dict:
+        """What this context's last Replica.patches_since observed (crdt_hip_patch_stats)."""
+        p, b, r, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().crdt_hip_patch_stats(self._h, C.byref(p), C.byref(b), C.byref(r),
+                                          C.byref(ns)), self._h)
+        return {"patches": int(p.value), "ins_bytes": int(b.value), "ranks": int(r.value),
                 "device_ns": int(ns.value)}
 
     def merge(self, log) -> tuple:
@@ -839,6 +926,24 @@ class Replica:
                                                  C.byref(a), C.byref(t)), self.ctx._h)
         return int(a.value), int(t.value)
 
+    def mark(self) -> Mark:
+        """Remember this version of the replica (crdt_hip_replica_mark): its tombstone bits packed
+        into a device bit plane the mark owns."""
+        h = C.c_void_p()
+        _check(lib().crdt_hip_replica_mark(self.ctx._h, self._h, C.byref(h)), self.ctx._h)
+        return Mark(h, self)
+
+    def patches_since_raw(self, mark: Mark) -> tuple:
+        """(crdt_hip_patch array as a structured numpy array, `ins` bytes) of
+        crdt_hip_replica_patches_since."""
+        return _patches_get(lambda *a: lib().crdt_hip_replica_patches_since(
+            self.ctx._h, self._h, mark._h, *a), self.ctx._h, guess=(4096, 1 << 16))
+
+    def patches_since(self, mark: Mark) -> list:
+        """OpLog.patches_since on the device (crdt_hip_replica_patches_since): the same patches.
+        Leaves the replica as a merge_inc would."""
+        return _patch_list(self.patches_since_raw(mark))
+
     def info(self) -> tuple:
         """(items, visible codepoints, visible UTF-8 bytes)."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -966,6 +1071,25 @@ class HipMerge:
         delta = other.log.encode_diff(self.log.state_vector())
         return self.log.apply_diff(delta) + (len(delta),)
 
+    def mark(self) -> Mark:
+        """Remember this version of the document (OpLog.mark)."""
+        return self.log.mark()
+
+    def patches_since(self, mark: Mark) -> list:
+        """What changed since `mark` as [(pos, del, ins)], the reference's TestPatch applied as
+        Upstream::replace (rope.rs:21-32): what an editor that keeps a text buffer beside this
+        adapter applies to it after a remote change."""
+        return self.log.patches_since(mark)
+
+    def sync_patches(self, other: "HipMerge") -> list:
+        """mark, sync_from(other), patches_since: the other's changes as positional edits."""
+        m = self.mark()
+        try:
+            self.sync_from(other)
+            return self.patches_since(m)
+        finally:
+            m.close()
+
 
 class HipDownstream:
     """`Downstream` (/root/reference/src/rope.rs:185-191) with the replica on the device.
@@ -1018,6 +1142,26 @@ class HipDownstream:
         other.flush()
         delta = other.replica.encode_diff(self.replica.state_vector())
         return self.replica.apply_diff(delta) + (len(delta),)
+
+    def mark(self) -> Mark:
+        """Remember this version of the document: the queued updates are decoded first
+        (Replica.mark)."""
+        self.flush()
+        return self.replica.mark()
+
+    def patches_since(self, mark: Mark) -> list:
+        """HipMerge.patches_since on the device: the queued updates are decoded first."""
+        self.flush()
+        return self.replica.patches_since(mark)
+
+    def sync_patches(self, other: "HipDownstream") -> list:
+        """mark, sync_from(other), patches_since: the other's changes as positional edits."""
+        m = self.mark()
+        try:
+            self.sync_from(other)
+            return self.patches_since(m)
+        finally:
+            m.close()
 
     def text(self) -> str:
         self.flush()

@@ -33,9 +33,26 @@ struct crdt_hip_ctx {
     std::vector<std::unique_ptr<crdt::ReplayState>> replays;
     crdt::JoinStats last_join;  // what the last crdt_hip_replica_join observed
     crdt::DeltaStats last_delta;  // what the last device encode_diff / apply_diff observed
+    crdt::PatchStats last_patch;  // what the last device patches_since observed
 };
+namespace {
+// Names the owner of a mark: every log and replica handle gets its own, a clone included.
+uint64_t next_uid() {
+    static std::atomic<uint64_t> n{0};
+    return ++n;
+}
+}  // namespace
 struct crdt_hip_oplog {
     crdt::OpLog log;
+    uint64_t uid = next_uid();
+    crdt_hip_oplog() = default;
+    crdt_hip_oplog(const crdt_hip_oplog& o) : log(o.log) {}
+};
+struct crdt_hip_mark {
+    uint64_t owner = 0;           // uid of the log or replica the mark was taken from
+    crdt_hip_ctx* ctx = nullptr;  // a replica's mark: its context (a host mark: null)
+    crdt::LogMark host;
+    crdt::DeviceMark dev;
 };
 struct crdt_hip_trace {
     crdt::Trace t;
@@ -48,6 +65,7 @@ struct crdt_hip_batch {
 struct crdt_hip_replica {
     crdt_hip_ctx* ctx = nullptr;
     crdt::Replica r;
+    uint64_t uid = next_uid();
 };
 
 struct crdt_hip_updates {
@@ -956,6 +974,79 @@ int crdt_hip_delta_stats(const crdt_hip_ctx* ctx, uint64_t* items, uint64_t* ran
     if (ranges) *ranges = ctx->last_delta.ranges;
     if (table_slots) *table_slots = ctx->last_delta.table_slots;
     if (device_ns) *device_ns = ctx->last_delta.device_ns;
+    return 0;
+}
+// ---- patches since a mark ------------------------------------------------------------------------
+static_assert(sizeof(crdt_hip_patch) == sizeof(crdt::PatchRec) && sizeof(crdt_hip_patch) == 24,
+              "patch layout");
+int crdt_hip_oplog_mark(const crdt_hip_oplog* log, crdt_hip_mark** out) {
+    if (!log || !out) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    *out = nullptr;
+    return guard(nullptr, [&] {
+        std::unique_ptr<crdt_hip_mark> m(new crdt_hip_mark());
+        m->owner = log->uid;
+        m->host = log->log.mark();
+        *out = m.release();
+        return 0;
+    });
+}
+void crdt_hip_mark_free(crdt_hip_mark* m) { delete m; }
+int crdt_hip_oplog_patches_since(crdt_hip_oplog* log, const crdt_hip_mark* m, crdt_hip_patch* out,
+                                 size_t cap, size_t* out_n, uint8_t* ins, size_t ins_cap,
+                                 size_t* out_ins) {
+    if (!log || !m || !out_n || !out_ins) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    if (m->ctx) return set_err(nullptr, CRDT_HIP_EINVAL, "a replica's mark passed to a log");
+    if (m->owner != log->uid) return set_err(nullptr, CRDT_HIP_EINVAL, "the mark belongs to another log");
+    return guard(nullptr, [&] {
+        std::vector<crdt::PatchRec> p;
+        std::vector<uint8_t> text;
+        std::string e;
+        const int rc = log->log.patches_since(m->host, p, text, e);
+        if (rc) return set_err(nullptr, rc, e);
+        *out_n = p.size();
+        *out_ins = text.size();
+        if ((!p.empty() && (!out || cap < p.size())) || (!text.empty() && (!ins || ins_cap < text.size())))
+            return set_err(nullptr, CRDT_HIP_ESPACE, "buffer too small");
+        if (!p.empty()) std::memcpy(out, p.data(), p.size() * sizeof(crdt::PatchRec));
+        if (!text.empty()) std::memcpy(ins, text.data(), text.size());
+        return 0;
+    });
+}
+int crdt_hip_replica_mark(crdt_hip_ctx* ctx, crdt_hip_replica* r, crdt_hip_mark** out) {
+    if (!ctx || !r || !out) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    *out = nullptr;
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    return guard(ctx, [&] {
+        std::unique_ptr<crdt_hip_mark> m(new crdt_hip_mark());
+        m->owner = r->uid;
+        m->ctx = ctx;
+        const int rc = crdt::replica_mark(ctx->eng, r->r, m->dev);
+        if (rc) return from_engine(ctx, rc);
+        *out = m.release();
+        return 0;
+    });
+}
+int crdt_hip_replica_patches_since(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_mark* m,
+                                   crdt_hip_patch* out, size_t cap, size_t* out_n, uint8_t* ins,
+                                   size_t ins_cap, size_t* out_ins) {
+    if (!ctx || !r || !m || !out_n || !out_ins) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    if (!m->ctx) return set_err(ctx, CRDT_HIP_EINVAL, "a log's mark passed to a replica");
+    if (m->ctx != ctx || m->owner != r->uid)
+        return set_err(ctx, CRDT_HIP_EINVAL, "the mark belongs to another replica");
+    return guard(ctx, [&] {
+        return from_engine(ctx, crdt::replica_patches_since(
+                                    ctx->eng, r->r, m->dev, reinterpret_cast<crdt::PatchRec*>(out), cap,
+                                    out_n, ins, ins_cap, out_ins, &ctx->last_patch));
+    });
+}
+int crdt_hip_patch_stats(const crdt_hip_ctx* ctx, uint64_t* patches, uint64_t* ins_bytes,
+                         uint64_t* ranks, uint64_t* device_ns) {
+    if (!ctx) return set_err(nullptr, CRDT_HIP_EINVAL, "null context");
+    if (patches) *patches = ctx->last_patch.patches;
+    if (ins_bytes) *ins_bytes = ctx->last_patch.ins_bytes;
+    if (ranks) *ranks = ctx->last_patch.ranks;
+    if (device_ns) *device_ns = ctx->last_patch.device_ns;
     return 0;
 }
 int crdt_hip_replica_info(const crdt_hip_replica* r, uint64_t* items,

@@ -41,6 +41,39 @@ struct Device {
     }
 };
 
+// One positional edit, the reference's TestPatch applied as Upstream::replace (rope.rs:21-32):
+// replace(pos..pos + del, ins), positions in codepoints.
+struct Patch {
+    size_t pos, del;
+    std::string ins;
+};
+// A version of one HipMerge or HipDownstream (crdt_hip_mark): valid for the object it was taken
+// from (a clone is another owner), across its later edits, updates, joins and deltas.
+struct MarkFree {
+    void operator()(crdt_hip_mark* m) const { crdt_hip_mark_free(m); }
+};
+using Mark = std::unique_ptr<crdt_hip_mark, MarkFree>;
+// call(out, cap, out_n, ins, ins_cap, out_ins) under the ESPACE convention -> the patches.
+// (cap0, ins0: first capacities to try; a device call streams the document order every time)
+template <class Call>
+std::vector<Patch> patches_get(Call&& call, crdt_hip_ctx* ctx, size_t cap0, size_t ins0) {
+    std::vector<crdt_hip_patch> p(cap0);
+    std::string text(ins0, '\0');
+    size_t n = 0, nb = 0;
+    int rc = call(p.data(), p.size(), &n, reinterpret_cast<uint8_t*>(text.data()), text.size(), &nb);
+    if (rc == CRDT_HIP_ESPACE) {
+        p.resize(n);
+        text.resize(nb);
+        rc = call(p.data(), p.size(), &n, reinterpret_cast<uint8_t*>(text.data()), text.size(), &nb);
+    }
+    check(rc, ctx, "patches_since");
+    std::vector<Patch> out;
+    out.reserve(n);
+    for (size_t k = 0; k < n; ++k)
+        out.push_back(Patch{(size_t)p[k].pos, p[k].del, text.substr((size_t)p[k].ins_off, p[k].ins_len)});
+    return out;
+}
+
 class HipMerge {
 public:
     static constexpr const char* NAME = "mi355x";
@@ -136,6 +169,20 @@ public:
     void apply_update(const Update& u) {
         check(crdt_hip_oplog_apply_update(log_.get(), u.data(), u.size()), nullptr, "apply_update");
     }
+    // Remember this version of the document; patches_since(mark) then gives what changed since,
+    // ascending in pos: what an editor that keeps a text buffer beside this applies to it.
+    Mark mark() const {
+        crdt_hip_mark* m = nullptr;
+        check(crdt_hip_oplog_mark(log_.get(), &m), nullptr, "oplog_mark");
+        return Mark(m);
+    }
+    std::vector<Patch> patches_since(const Mark& m) const {
+        return patches_get(
+            [&](crdt_hip_patch* out, size_t cap, size_t* n, uint8_t* ins, size_t icap, size_t* nb) {
+                return crdt_hip_oplog_patches_since(log_.get(), m.get(), out, cap, n, ins, icap, nb);
+            },
+            nullptr, 0, 0);
+    }
 
 private:
     struct Free {
@@ -221,6 +268,22 @@ public:
               dev_->ctx, "replica_merge");
         out.resize(n);
         return out;
+    }
+    // HipMerge::mark / patches_since on the device (the queued updates are decoded first).
+    Mark mark() const {
+        flush();
+        crdt_hip_mark* m = nullptr;
+        check(crdt_hip_replica_mark(dev_->ctx, rep_, &m), dev_->ctx, "replica_mark");
+        return Mark(m);
+    }
+    std::vector<Patch> patches_since(const Mark& m) const {
+        flush();
+        return patches_get(
+            [&](crdt_hip_patch* out, size_t cap, size_t* n, uint8_t* ins, size_t icap, size_t* nb) {
+                return crdt_hip_replica_patches_since(dev_->ctx, rep_, m.get(), out, cap, n, ins,
+                                                      icap, nb);
+            },
+            dev_->ctx, 4096, 1 << 16);
     }
 
 private:

@@ -662,6 +662,14 @@ void OpLog::mark_deleted(uint32_t id) {
 // items arrived.  Host resolver bookkeeping only: merged documents always come from the device.
 std::string OpLog::rebuild_index() {
     if (fugue) return rebuild_index_fugue();
+    std::vector<uint32_t> order;
+    std::string e = order_rga(order);
+    if (!e.empty()) return e;
+    return rebuild_index_rga(order);
+}
+
+// The RGA pre-order of every item (tombstones included), from the log alone.
+std::string OpLog::order_rga(std::vector<uint32_t>& order) const {
     uint32_t n = size();
     std::vector<uint32_t> start(n + 2, 0), kids(n);
     for (uint32_t i = 1; i <= n; ++i) {
@@ -678,7 +686,7 @@ std::string OpLog::rebuild_index() {
         if (lamport[a - 1] != lamport[b - 1]) return lamport[a - 1] > lamport[b - 1];
         return agent[a - 1] > agent[b - 1];
     };
-    std::vector<uint32_t> order;
+    order.clear();
     order.reserve(n);
     std::vector<uint32_t> stack;
     stack.reserve(n + 1);
@@ -692,7 +700,7 @@ std::string OpLog::rebuild_index() {
         for (uint32_t j = a; j < b; ++j) stack.push_back(kids[j]);  // oldest pushed first
     }
     if (order.size() != n) return "malformed op log (cycle)";
-    return rebuild_index_rga(order);
+    return "";
 }
 
 // Appends item v to the end of the rebuilt sequence.
@@ -717,6 +725,26 @@ void OpLog::index_append(uint32_t v) {
 // hasright_ with the remote right children.
 std::string OpLog::rebuild_index_fugue() {
     const uint32_t n = size();
+    std::vector<uint32_t> order;
+    std::string e = order_fugue(order);
+    if (!e.empty()) return e;
+    hasright_.assign(std::max<size_t>(hasright_.size(), (size_t)n + 1), 0);
+    for (uint32_t i = 1; i <= n; ++i)
+        if (!side[i - 1]) hasright_[parent[i - 1]] = 1;
+    chunks_.clear();
+    chunks_.push_back(new_chunk());
+    nvis_ = 0;
+    hint_c_ = SIZE_MAX;
+    hint_si_ = SIZE_MAX;
+    for (uint32_t id : order) index_append(id);
+    fen_build();
+    stale_ = false;
+    return "";
+}
+
+// The Fugue in-order of every item (tombstones included), from the log alone.
+std::string OpLog::order_fugue(std::vector<uint32_t>& order) const {
+    const uint32_t n = size();
     if (side.size() != n) return "malformed op log (side column)";
     std::vector<uint32_t> start(2ull * n + 3, 0), kids(n);  // groups 2v (left), 2v + 1 (right)
     for (uint32_t i = 1; i <= n; ++i) {
@@ -729,29 +757,21 @@ std::string OpLog::rebuild_index_fugue() {
         std::vector<uint32_t> fill(start.begin(), start.end() - 1);
         for (uint32_t i = 1; i <= n; ++i) kids[fill[2ull * parent[i - 1] + (side[i - 1] ? 0 : 1)]++] = i;
     }
-    hasright_.assign(std::max<size_t>(hasright_.size(), (size_t)n + 1), 0);
-    for (uint32_t i = 1; i <= n; ++i)
-        if (!side[i - 1]) hasright_[parent[i - 1]] = 1;
     auto older = [&](uint32_t a, uint32_t b) {  // a has the smaller timestamp
         if (lamport[a - 1] != lamport[b - 1]) return lamport[a - 1] < lamport[b - 1];
         return agent[a - 1] < agent[b - 1];
     };
-    chunks_.clear();
-    chunks_.push_back(new_chunk());
-    nvis_ = 0;
-    hint_c_ = SIZE_MAX;
-    hint_si_ = SIZE_MAX;
+    order.clear();
+    order.reserve(n);
     constexpr uint32_t EMIT = 0x80000000u;
     std::vector<uint32_t> stack;
     stack.reserve(2ull * n + 2);
     stack.push_back(0);
-    size_t seen = 0;
     while (!stack.empty()) {
         const uint32_t e = stack.back();
         stack.pop_back();
         if (e & EMIT) {
-            ++seen;
-            index_append(e & ~EMIT);
+            order.push_back(e & ~EMIT);
             continue;
         }
         // pushed in reverse of the walk: right children, e, left children (each oldest first)
@@ -762,10 +782,61 @@ std::string OpLog::rebuild_index_fugue() {
         if (e) stack.push_back(e | EMIT);
         for (uint32_t j = l0; j < l1; ++j) stack.push_back(kids[j]);
     }
-    if (seen != n) return "malformed op log (cycle)";
-    fen_build();
-    stale_ = false;
+    if (order.size() != n) return "malformed op log (cycle)";
     return "";
+}
+
+std::string OpLog::document_order(std::vector<uint32_t>& order) const {
+    return fugue ? order_fugue(order) : order_rga(order);
+}
+
+LogMark OpLog::mark() const {
+    LogMark m;
+    m.n = size();
+    m.deleted.assign(deleted.begin(), deleted.end());
+    return m;
+}
+
+int OpLog::patches_since(const LogMark& m, std::vector<PatchRec>& out, std::vector<uint8_t>& ins,
+                         std::string& err) const {
+    out.clear();
+    ins.clear();
+    if (size() < m.n || m.deleted.size() != m.n) {
+        err = "the log holds fewer items than the mark";
+        return CRDT_HIP_EINVAL;
+    }
+    std::vector<uint32_t> order;
+    err = document_order(order);
+    if (!err.empty()) return CRDT_HIP_EBADLOG;
+    uint64_t pos = 0;   // `now` items so far
+    bool open = false;  // the previous K, D or I item was a D or an I: its run goes on
+    for (uint32_t id : order) {
+        const bool was = id <= m.n && !m.deleted[id - 1], now = !deleted[id - 1];
+        if (!was && !now) continue;
+        if (was && now) {
+            ++pos;
+            open = false;
+            continue;
+        }
+        if (!open) {
+            out.push_back(PatchRec{pos, (uint64_t)ins.size(), 0u, 0u});
+            open = true;
+        }
+        if (was) {
+            out.back().del++;
+        } else {
+            char b[4];
+            const size_t k = utf8_put(cp[id - 1], b);
+            ins.insert(ins.end(), b, b + k);
+            out.back().ins_len += (uint32_t)k;
+            ++pos;
+            if (ins.size() >= (1ull << 32)) {
+                err = "4 GiB or more of inserted bytes";
+                return CRDT_HIP_ERANGE;
+            }
+        }
+    }
+    return CRDT_HIP_OK;
 }
 
 // Wire format (little-endian): magic, version, first_id, n_items, first_del, n_dels,

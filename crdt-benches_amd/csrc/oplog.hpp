@@ -80,6 +80,18 @@ struct DeltaFrame {
 int delta_frame(const uint8_t* buf, size_t len, bool fugue, uint64_t held, DeltaFrame& f,
                 std::string& err);
 
+// Patches since a mark (crdt_hip.h, "patches since a mark"; the device twin is patch.hip).
+// A mark is a version of one log: its item count and every item's tombstone at that time.
+struct LogMark {
+    uint32_t n = 0;
+    std::vector<uint8_t> deleted;  // n entries
+};
+// One positional edit, layout of crdt_hip_patch: replace(pos..pos + del, ins[ins_off, +ins_len)).
+struct PatchRec {
+    uint64_t pos, ins_off;
+    uint32_t del, ins_len;
+};
+
 class OpLog {
 public:
     // ---- SoA (index k holds item id k+1) ----
@@ -150,6 +162,18 @@ public:
     int apply_diff(const uint8_t* buf, size_t len, uint32_t* added, uint32_t* tombstoned,
                    std::string& err);
 
+    // Patches since a mark: what changed in the document between the mark and now, as positional
+    // edits in ascending position (the semantics are stated in crdt_hip.h).  The document order
+    // comes from the log itself (document_order), never from the positional index, which a call
+    // neither reads nor touches.  CRDT_HIP_EINVAL when the log holds fewer items than the mark,
+    // EBADLOG for a malformed log, ERANGE for 4 GiB or more of inserted bytes.
+    LogMark mark() const;
+    int patches_since(const LogMark& m, std::vector<PatchRec>& out, std::vector<uint8_t>& ins,
+                      std::string& err) const;
+    // Every item id in document order, tombstones included (RGA pre-order or Fugue in-order): the
+    // sibling sort and walk that rebuild_index / rebuild_index_fugue build their index from.
+    std::string document_order(std::vector<uint32_t>& order) const;
+
     // Append a fully-specified item (synthetic generators / decoding); marks the positional
     // index stale.
     void push_item(uint32_t par, uint32_t orr, uint32_t lam, uint16_t ag, uint8_t del,
@@ -219,6 +243,8 @@ private:
     bool split_chunk(size_t c);  // true if chunk c was split in two
     std::string rebuild_index();
     std::string rebuild_index_fugue();
+    std::string order_rga(std::vector<uint32_t>& order) const;
+    std::string order_fugue(std::vector<uint32_t>& order) const;
     void index_append(uint32_t v);
     // p-th visible item (p >= 1): chunk c, span si, offset off inside the span.
     bool find_visible(uint64_t p, size_t& c, size_t& si, uint32_t& off) const;

@@ -200,6 +200,37 @@ int replica_encode_diff(Engine& E, const Replica& r, const SvEntry* sv, size_t n
 int replica_apply_diff(Engine& E, Replica& dst, const uint8_t* buf, size_t len, uint32_t* added,
                        uint32_t* tombstoned, DeltaStats* stats = nullptr);
 
+// Patches since a mark (patch.hip; semantics in crdt_hip.h, host twin OpLog::patches_since): what
+// changed in the replica's document between a mark and now, as positional edits.
+constexpr uint32_t kPatchTile = 4096;  // consecutive ranks of the document order per workgroup
+// A version of one replica: its item count and a device bit plane of n + 1 bits, 1 = the slot was
+// tombstoned or is not an item (slot 0, and the padding of the last word).  Owns the buffer.
+struct DeviceMark {
+    uint32_t n = 0;
+    uint64_t words = 0;
+    uint64_t* bits = nullptr;
+    DeviceMark() = default;
+    DeviceMark(const DeviceMark&) = delete;
+    DeviceMark& operator=(const DeviceMark&) = delete;
+    ~DeviceMark();
+};
+struct PatchStats {  // what the last device patches_since observed (crdt_hip_patch_stats)
+    uint64_t patches = 0;    // patches found
+    uint64_t ins_bytes = 0;  // their inserted UTF-8 bytes
+    uint64_t ranks = 0;      // ranks of the document order streamed (the items held)
+    uint64_t device_ns = 0;  // summed device time of the call's kernels (HIP events)
+};
+struct PatchRec;
+// Settles a pending decode, then packs the tombstone bits of slots 0..n (k_mark_pack).
+int replica_mark(Engine& E, Replica& r, DeviceMark& m);
+// Brings r.inc up to date as replica_merge_inc does (so a call leaves the replica as a merge_inc
+// would), then classifies, scans and compacts over the kept order.  *out_n / *out_ins: patches
+// and inserted bytes; ESPACE (before the write pass) when out / ins are null or short.  EINVAL
+// when the replica holds fewer items than the mark, ERANGE for 4 GiB or more of inserted bytes.
+int replica_patches_since(Engine& E, Replica& r, const DeviceMark& m, PatchRec* out, size_t cap,
+                          size_t* out_n, uint8_t* ins, size_t ins_cap, size_t* out_ins,
+                          PatchStats* stats = nullptr);
+
 // Incremental merge (incr.hip): the merged text (may be null), its UTF-8 bytes and codepoints;
 // *path = 1 when only the items appended since the previous merge_inc were ranked, 0 for a
 // full merge (the first call, a concurrent update, more than kIncMax new items, Fugue).

@@ -24,6 +24,11 @@
  *                        -> crdt_hip_oplog_state_vector / _encode_diff / _apply_diff, or on the
  *                           device crdt_hip_replica_state_vector / _encode_diff / _apply_diff:
  *                           divergent logs exchange only what the other lacks ("delta sync")
+ *   TestPatch(pos, del, ins) / replace (rope.rs:21-32), the other way round
+ *                        -> crdt_hip_oplog_mark + crdt_hip_oplog_patches_since, or on the device
+ *                           crdt_hip_replica_mark + crdt_hip_replica_patches_since: what an update,
+ *                           a join or a delta changed in the document, as positional edits for an
+ *                           editor that keeps a text buffer beside the log ("patches since a mark")
  *
  * Conventions
  *   - Every function returns int status: 0 = ok, < 0 = error (CRDT_HIP_E*).  Nothing throws or
@@ -312,6 +317,58 @@ int crdt_hip_oplog_encode_diff(const crdt_hip_oplog* log, const crdt_hip_sv_entr
 int crdt_hip_oplog_apply_diff(crdt_hip_oplog* log, const uint8_t* buf, size_t len,
                               uint32_t* added, uint32_t* tombstoned);
 
+/* ---- patches since a mark: what a sync changed, as positional edits ---------------------------
+ * After an update, a join or a delta the log is right, but an editor that keeps a text buffer
+ * beside it needs the remote change in the reference's own unit, TestPatch(pos, del, ins) applied
+ * as Upstream::replace (rope.rs:21-32).  The resolver turns positions into identities; this turns
+ * identities back into positions, on the host (crdt_hip_oplog_*) and in HIP kernels on the device
+ * (crdt_hip_replica_*, below), with identical results.
+ *
+ * A mark remembers a version of one log or one replica: the item count n_mark and, for every item
+ * 1..n_mark, whether it was deleted.  Slots are append-only and tombstones are only ever set, so
+ * that describes the earlier version in full.
+ *
+ * Patches since a mark are defined over the current document order of all items held, tombstones
+ * included (RGA pre-order or Fugue in-order).  For item s:
+ *   was = s <= n_mark and not deleted at the mark;   now = not deleted now.
+ * Items that are neither are dropped.  The rest are K = was and now, D = was and not now,
+ * I = not was and now (tombstones never clear, so I implies s > n_mark).  A patch is a maximal
+ * run of consecutive non-K items of that filtered sequence:
+ *   pos = the now items (K or I) before the run, in codepoints;
+ *   del = the D items of the run;
+ *   ins = the UTF-8 of the run's I items, in order.
+ * Patches come out ascending in pos.  Applied in that order, each as replace(pos..pos + del, ins),
+ * to the document at the mark, they give the current document.  Hence:
+ *   - an item inserted and deleted after the mark appears in no patch;
+ *   - a run that interleaves D and I items is one patch (one side deleted a stretch, the other
+ *     typed inside it);
+ *   - two patches never touch: pos[k + 1] > pos[k] + codepoints(ins[k]);
+ *   - nothing changed means zero patches.
+ *
+ * ins_off / ins_len are bytes into `ins`; ins_off ascends and the pieces are contiguous.  Output
+ * buffers follow crdt_hip_oplog_encode_from: a NULL or short `out` or `ins` sets *out_n (patches)
+ * and *out_ins (bytes) to the need and returns CRDT_HIP_ESPACE.
+ * A mark belongs to the log or replica it was taken from and stays valid across every later
+ * update, join, delta and local edit of that owner; several marks may be alive at once; taking or
+ * using one changes no log contents (a host call neither reads nor disturbs the resolver index).
+ * Free a mark with crdt_hip_mark_free (before the context of a replica mark is destroyed).
+ *   CRDT_HIP_EINVAL  a mark of another owner (a clone is another owner); a host mark passed to a
+ *                    replica call or the reverse; a replica of another context; an owner with
+ *                    fewer items than the mark
+ *   CRDT_HIP_ERANGE  2^32 or more patches, or 4 GiB or more of inserted bytes */
+typedef struct crdt_hip_mark crdt_hip_mark;
+typedef struct {
+    uint64_t pos;     /* codepoints before the patch in the current document */
+    uint64_t ins_off; /* byte offset of the inserted text in `ins` */
+    uint32_t del;     /* codepoints deleted at pos */
+    uint32_t ins_len; /* bytes inserted at pos */
+} crdt_hip_patch;
+int crdt_hip_oplog_mark(const crdt_hip_oplog* log, crdt_hip_mark** out);
+void crdt_hip_mark_free(crdt_hip_mark* m);
+int crdt_hip_oplog_patches_since(crdt_hip_oplog* log, const crdt_hip_mark* m, crdt_hip_patch* out,
+                                 size_t cap, size_t* out_n, uint8_t* ins, size_t ins_cap,
+                                 size_t* out_ins);
+
 /* ---- trace loader (crdt-testdata load_testing_data / chars_to_bytes, main.rs:19-23) ---------- */
 int crdt_hip_trace_load(const char* path, crdt_hip_trace** out);
 void crdt_hip_trace_free(crdt_hip_trace* t);
@@ -479,6 +536,28 @@ int crdt_hip_replica_apply_diff(crdt_hip_ctx* ctx, crdt_hip_replica* r, const ui
  * encode), and the summed device time of the call's kernels in ns (HIP events). */
 int crdt_hip_delta_stats(const crdt_hip_ctx* ctx, uint64_t* items, uint64_t* ranges,
                          uint64_t* table_slots, uint64_t* device_ns);
+/* Patches since a mark on the device (see "patches since a mark" above): the same patch array and
+ * the same `ins` bytes as the host calls, from HIP kernels on the context's stream; no host copy
+ * of the replica's columns is made.  crdt_hip_replica_mark settles a pending decode, then packs
+ * the tombstone bits of the replica into a device bit plane the mark owns.
+ * crdt_hip_replica_patches_since first brings the replica's kept document order up to date exactly
+ * as crdt_hip_replica_merge_inc does (the incremental path where it applies, a full ORDER-mode
+ * merge otherwise, as after a join or a delta), so a call leaves the replica as a merge_inc would.
+ * It then classifies every rank of that order (each workgroup a tile of at most 4,096 consecutive
+ * ranks), scans the tile aggregates in one workgroup, waits once for the totals that size the
+ * outputs (CRDT_HIP_ESPACE is returned here, before the write pass), and compacts the patches and
+ * their text in order.  Known cost: a call streams every rank of the replica however small the
+ * change. */
+int crdt_hip_replica_mark(crdt_hip_ctx* ctx, crdt_hip_replica* r, crdt_hip_mark** out);
+int crdt_hip_replica_patches_since(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_mark* m,
+                                   crdt_hip_patch* out, size_t cap, size_t* out_n, uint8_t* ins,
+                                   size_t ins_cap, size_t* out_ins);
+/* What the context's last crdt_hip_replica_patches_since observed (each may be NULL): patches
+ * found, their inserted bytes, ranks of the document order streamed (the items held), and the
+ * summed device time of the call's own kernels in ns (HIP events; the order update is not
+ * included). */
+int crdt_hip_patch_stats(const crdt_hip_ctx* ctx, uint64_t* patches, uint64_t* ins_bytes,
+                         uint64_t* ranks, uint64_t* device_ns);
 /* Items held, visible codepoints (Upstream::len, rope.rs:16-19) and visible UTF-8 bytes. */
 int crdt_hip_replica_info(const crdt_hip_replica* r, uint64_t* items,
                           uint64_t* visible_codepoints, uint64_t* visible_bytes);
