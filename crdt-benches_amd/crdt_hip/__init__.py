@@ -57,6 +57,8 @@ EXPORTS = [
     "crdt_hip_replica_apply_diff", "crdt_hip_delta_stats",
     "crdt_hip_oplog_mark", "crdt_hip_mark_free", "crdt_hip_oplog_patches_since",
     "crdt_hip_replica_mark", "crdt_hip_replica_patches_since", "crdt_hip_patch_stats",
+    "crdt_hip_oplog_apply_patches", "crdt_hip_replica_set_agent",
+    "crdt_hip_replica_apply_patches", "crdt_hip_replica_replace", "crdt_hip_edit_stats",
 ]
 
 
@@ -187,6 +189,11 @@ def lib() -> C.CDLL:
         "crdt_hip_replica_mark": (i32, [vp, vp, P(vp)]),
         "crdt_hip_replica_patches_since": (i32, [vp, vp, vp, vp, sz, P(sz), vp, sz, P(sz)]),
         "crdt_hip_patch_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64)]),
+        "crdt_hip_oplog_apply_patches": (i32, [vp, vp, sz, vp, sz, P(u32), P(u32)]),
+        "crdt_hip_replica_set_agent": (i32, [vp, C.c_uint16]),
+        "crdt_hip_replica_apply_patches": (i32, [vp, vp, vp, sz, vp, sz, P(u32), P(u32)]),
+        "crdt_hip_replica_replace": (i32, [vp, vp, sz, sz, C.c_char_p, sz]),
+        "crdt_hip_edit_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge": (i32, [vp, vp, vp, sz, P(sz), P(u64)]),
         "crdt_hip_replica_merge_len": (i32, [vp, vp, P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge_inc": (i32, [vp, vp, vp, sz, P(sz), P(u64), P(u32)]),
@@ -373,6 +380,23 @@ def _patch_list(raw: tuple) -> list:
             for p in arr]
 
 
+def _patches_pack(patches, ins=None) -> tuple:
+    """The arguments of an apply_patches call -> (crdt_hip_patch array, `ins` bytes).  `patches`:
+    [(pos, del, ins: str)] as patches_since returns them (`ins` None), or a structured array of
+    PATCH_DTYPE with its `ins` bytes (the raw form, passed through unchecked)."""
+    if ins is not None:
+        return np.ascontiguousarray(patches, dtype=PATCH_DTYPE), bytes(ins)
+    plist = list(patches)
+    arr = np.zeros(len(plist), PATCH_DTYPE)
+    parts, off = [], 0
+    for k, (pos, dele, text) in enumerate(plist):
+        b = text.encode("utf-8")
+        arr[k] = (pos, off, dele, len(b))
+        parts.append(b)
+        off += len(b)
+    return arr, b"".join(parts)
+
+
 class OpLog:
     """Host-side resolver (positional patches -> anchor op log), crdt_hip_oplog_*."""
 
@@ -500,6 +524,18 @@ class OpLog:
         applied in that order, each as replace(pos, pos + del, ins), to the text at the mark they
         give the text now (crdt_hip_oplog_patches_since)."""
         return _patch_list(self.patches_since_raw(mark))
+
+    def apply_patches(self, patches, ins=None) -> tuple:
+        """Local edits as a set of positional patches in the patches_since convention
+        (crdt_hip_oplog_apply_patches): [(pos, del, ins: str)] ascending and non-touching, each
+        applied as replace(pos, pos + del, ins) to the document as the earlier ones left it.
+        Returns (items appended, items deleted); a rejected call raises and changes nothing."""
+        arr, text = _patches_pack(patches, ins)
+        a, t = C.c_uint32(), C.c_uint32()
+        _check(lib().crdt_hip_oplog_apply_patches(
+            self._h, arr.ctypes.data if arr.size else None, arr.size, text, len(text),
+            C.byref(a), C.byref(t)))
+        return int(a.value), int(t.value)
 
     def save(self, path: str) -> None:
         """Op-log file (crdt_hip_oplog_save): 64-byte-aligned SoA arrays."""
@@ -678,6 +714,15 @@ class Context:
                                           C.byref(ns)), self._h)
         return {"patches": int(p.value), "ins_bytes": int(b.value), "ranks": int(r.value),
                 "device_ns": int(ns.value)}
+
+    def edit_stats(self) -> dict:
+        """What this context's last Replica.apply_patches (or replace, insert, remove) observed
+        (crdt_hip_edit_stats)."""
+        p, i, t, r, ns = (C.c_uint64() for _ in range(5))
+        _check(lib().crdt_hip_edit_stats(self._h, C.byref(p), C.byref(i), C.byref(t), C.byref(r),
+                                         C.byref(ns)), self._h)
+        return {"patches": int(p.value), "items": int(i.value), "tombstones": int(t.value),
+                "ranks": int(r.value), "device_ns": int(ns.value)}
 
     def merge(self, log) -> tuple:
         """Merged document: (utf8 bytes, tree digest)."""
@@ -944,6 +989,37 @@ class Replica:
         Leaves the replica as a merge_inc would."""
         return _patch_list(self.patches_since_raw(mark))
 
+    def set_agent(self, agent: int) -> None:
+        """The agent id of this replica's later local edits (crdt_hip_replica_set_agent; default
+        0, kept by a clone)."""
+        _check(lib().crdt_hip_replica_set_agent(self._h, agent))
+
+    def apply_patches(self, patches, ins=None) -> tuple:
+        """OpLog.apply_patches on the device (crdt_hip_replica_apply_patches): the same resulting
+        log, slot for slot, with the positions resolved in HIP kernels against the replica's kept
+        document order.  Returns (items appended, items deleted); a rejected call raises and
+        changes nothing."""
+        arr, text = _patches_pack(patches, ins)
+        a, t = C.c_uint32(), C.c_uint32()
+        _check(lib().crdt_hip_replica_apply_patches(
+            self.ctx._h, self._h, arr.ctypes.data if arr.size else None, arr.size, text, len(text),
+            C.byref(a), C.byref(t)), self.ctx._h)
+        return int(a.value), int(t.value)
+
+    def replace(self, start: int, end: int, text: str) -> None:
+        """Upstream::replace on the device (crdt_hip_replica_replace): one patch."""
+        b = text.encode("utf-8")
+        _check(lib().crdt_hip_replica_replace(self.ctx._h, self._h, start, end, b, len(b)),
+               self.ctx._h)
+
+    def insert(self, pos: int, text: str) -> None:
+        self.replace(pos, pos, text)
+
+    def remove(self, start: int, end: int) -> None:
+        if end < start:
+            raise CrdtHipError(-2, "remove range out of range")
+        self.replace(start, end, "")
+
     def info(self) -> tuple:
         """(items, visible codepoints, visible UTF-8 bytes)."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -1096,7 +1172,9 @@ class HipDownstream:
 
     apply_update() queues the encoded update on the host; len() decodes every queued update on
     the device in one batch (crdt_hip_replica_apply_updates), merges the replica there and
-    returns its visible codepoints.  clone() copies the replica device to device.  This is the
+    returns its visible codepoints.  clone() copies the replica device to device.  It is an
+    `Upstream` (rope.rs:6-33) too: from_str, insert, remove and replace resolve the edit on the
+    device (crdt_hip_replica_replace), so no host log is kept beside the replica.  This is the
     shape of the Rust adapter in INTEGRATION.md.
     """
 
@@ -1112,6 +1190,27 @@ class HipDownstream:
         up, updates = HipMerge.upstream_updates(start_content, patches)
         ctx = HipMerge.context()
         return cls(Replica(ctx, up.log if up.log.view().n else None)), updates
+
+    # Upstream (rope.rs:6-33) on the device: the queued updates are decoded first, then the edit
+    # is resolved against the replica where it lies (Replica.replace); no host log is kept
+    @classmethod
+    def from_str(cls, s: str) -> "HipDownstream":
+        d = cls(Replica(HipMerge.context()))
+        if s:
+            d.insert(0, s)
+        return d
+
+    def insert(self, at: int, text: str) -> None:
+        self.flush()
+        self.replica.insert(at, text)
+
+    def remove(self, start: int, end: int) -> None:
+        self.flush()
+        self.replica.remove(start, end)
+
+    def replace(self, start: int, end: int, text: str) -> None:
+        self.flush()
+        self.replica.replace(start, end, text)
 
     def clone(self) -> "HipDownstream":
         c = HipDownstream(self.replica.clone())

@@ -34,6 +34,7 @@ struct crdt_hip_ctx {
     crdt::JoinStats last_join;  // what the last crdt_hip_replica_join observed
     crdt::DeltaStats last_delta;  // what the last device encode_diff / apply_diff observed
     crdt::PatchStats last_patch;  // what the last device patches_since observed
+    crdt::EditStats last_edit;    // what the last device apply_patches observed
 };
 namespace {
 // Names the owner of a mark: every log and replica handle gets its own, a clone included.
@@ -1047,6 +1048,58 @@ int crdt_hip_patch_stats(const crdt_hip_ctx* ctx, uint64_t* patches, uint64_t* i
     if (ins_bytes) *ins_bytes = ctx->last_patch.ins_bytes;
     if (ranks) *ranks = ctx->last_patch.ranks;
     if (device_ns) *device_ns = ctx->last_patch.device_ns;
+    return 0;
+}
+// ---- local edits: positional patches into a log or a replica ---------------------------------------
+int crdt_hip_oplog_apply_patches(crdt_hip_oplog* log, const crdt_hip_patch* p, size_t n,
+                                 const uint8_t* ins, size_t ins_len, uint32_t* added,
+                                 uint32_t* tombstoned) {
+    if (!log || (!p && n) || (!ins && ins_len)) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    return guard(nullptr, [&] {
+        std::string e;
+        const int rc = log->log.apply_patches(reinterpret_cast<const crdt::PatchRec*>(p), n, ins,
+                                              ins_len, added, tombstoned, e);
+        return rc ? set_err(nullptr, rc, e) : 0;
+    });
+}
+int crdt_hip_replica_set_agent(crdt_hip_replica* r, uint16_t agent) {
+    if (!r) return set_err(nullptr, CRDT_HIP_EINVAL, "null replica");
+    r->r.agent = agent;
+    return 0;
+}
+int crdt_hip_replica_apply_patches(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_patch* p,
+                                   size_t n, const uint8_t* ins, size_t ins_len, uint32_t* added,
+                                   uint32_t* tombstoned) {
+    if (!ctx || !r || (!p && n) || (!ins && ins_len)) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    return guard(ctx, [&] {
+        return from_engine(ctx, crdt::replica_apply_patches(
+                                    ctx->eng, r->r, reinterpret_cast<const crdt::PatchRec*>(p), n, ins,
+                                    ins_len, added, tombstoned, &ctx->last_edit));
+    });
+}
+int crdt_hip_replica_replace(crdt_hip_ctx* ctx, crdt_hip_replica* r, size_t start, size_t end,
+                             const char* utf8, size_t nbytes) {
+    if (!ctx || !r || (!utf8 && nbytes)) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    // Upstream::replace (rope.rs:21-32), as crdt_hip_oplog_replace: remove if end > start, insert
+    // if the text is non-empty, nothing otherwise
+    const size_t del = end > start ? end - start : 0;
+    if (del == 0 && nbytes == 0) return 0;
+    if (del > 0xFFFFFFFFull || nbytes > 0xFFFFFFFFull)
+        return set_err(ctx, CRDT_HIP_ERANGE, "replace of 2^32 or more codepoints or bytes");
+    const crdt_hip_patch one{(uint64_t)start, 0, (uint32_t)del, (uint32_t)nbytes};
+    return crdt_hip_replica_apply_patches(ctx, r, &one, 1, reinterpret_cast<const uint8_t*>(utf8),
+                                          nbytes, nullptr, nullptr);
+}
+int crdt_hip_edit_stats(const crdt_hip_ctx* ctx, uint64_t* patches, uint64_t* items,
+                        uint64_t* tombstones, uint64_t* ranks, uint64_t* device_ns) {
+    if (!ctx) return set_err(nullptr, CRDT_HIP_EINVAL, "null context");
+    if (patches) *patches = ctx->last_edit.patches;
+    if (items) *items = ctx->last_edit.items;
+    if (tombstones) *tombstones = ctx->last_edit.tombstones;
+    if (ranks) *ranks = ctx->last_edit.ranks;
+    if (device_ns) *device_ns = ctx->last_edit.device_ns;
     return 0;
 }
 int crdt_hip_replica_info(const crdt_hip_replica* r, uint64_t* items,

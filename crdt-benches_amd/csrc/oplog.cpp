@@ -839,6 +839,91 @@ int OpLog::patches_since(const LogMark& m, std::vector<PatchRec>& out, std::vect
     return CRDT_HIP_OK;
 }
 
+// ---- local edits as positional patches ---------------------------------------------------------
+int edit_plan(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len, uint64_t visible,
+              uint64_t items, EditPlan& plan, std::string& err) {
+    plan.patch.clear();
+    plan.cps.clear();
+    plan.ndel = 0;
+    if (n >= (1ull << 31)) {
+        err = "2^31 or more patches";
+        return CRDT_HIP_ERANGE;
+    }
+    plan.patch.reserve(n);
+    uint64_t len = visible;   // the document as the earlier patches left it
+    uint64_t next_min = 0;    // pos[k] must exceed pos[k - 1] + codepoints(ins[k - 1])
+    int64_t shift = 0;        // sum of (codepoints inserted - deleted) of the earlier patches
+    for (size_t k = 0; k < n; ++k) {
+        const PatchRec& r = p[k];
+        if (r.del == 0 && r.ins_len == 0) {
+            err = "empty patch";
+            return CRDT_HIP_EINVAL;
+        }
+        if (r.ins_off > ins_len || r.ins_len > ins_len - r.ins_off || (r.ins_len && !ins)) {
+            err = "patch text outside the ins buffer";
+            return CRDT_HIP_EINVAL;
+        }
+        const size_t c0 = plan.cps.size();
+        if (r.ins_len && !utf8_decode(reinterpret_cast<const char*>(ins) + r.ins_off, r.ins_len, plan.cps)) {
+            err = "invalid UTF-8";
+            return CRDT_HIP_EINVAL;
+        }
+        const uint64_t ncp = plan.cps.size() - c0;
+        if (k && r.pos < next_min) {
+            err = "patches are not ascending and non-touching";
+            return CRDT_HIP_EINVAL;
+        }
+        if (r.pos > len || r.del > len - r.pos) {
+            err = "patch range beyond the document";
+            return CRDT_HIP_ERANGE;
+        }
+        if (items + plan.cps.size() >= 0x7FFFFFF0ull) {
+            err = "op log too large";
+            return CRDT_HIP_ERANGE;
+        }
+        EditPatch e;
+        e.old_pos = (uint32_t)((int64_t)r.pos - shift);
+        e.del = r.del;
+        e.cp0 = (uint32_t)c0;
+        e.ncp = (uint32_t)ncp;
+        e.del0 = (uint32_t)plan.ndel;
+        e.pad = 0;
+        plan.patch.push_back(e);
+        plan.ndel += r.del;
+        len = len - r.del + ncp;
+        shift += (int64_t)ncp - (int64_t)r.del;
+        next_min = r.pos + ncp + 1;
+    }
+    return CRDT_HIP_OK;
+}
+
+int OpLog::apply_patches(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
+                         uint32_t* added, uint32_t* tombstoned, std::string& err) {
+    if (added) *added = 0;
+    if (tombstoned) *tombstoned = 0;
+    if (n == 0) return CRDT_HIP_OK;
+    EditPlan plan;
+    const int rc = edit_plan(p, n, ins, ins_len, nvis_, size(), plan, err);
+    if (rc) return rc;
+    if ((uint64_t)max_lamport + plan.cps.size() >= 0xFFFFFFFFull) {
+        err = "lamports would reach 0xFFFFFFFF";
+        return CRDT_HIP_ERANGE;
+    }
+    if (stale_) {  // (a malformed log is found here, before anything changes)
+        err = rebuild_index();
+        if (!err.empty()) return CRDT_HIP_EBADLOG;
+    }
+    for (size_t k = 0; k < n; ++k) {
+        const EditPatch& e = plan.patch[k];
+        if (p[k].del) err = remove(p[k].pos, p[k].pos + p[k].del);
+        if (err.empty() && e.ncp) err = insert(p[k].pos, plan.cps.data() + e.cp0, e.ncp);
+        if (!err.empty()) return CRDT_HIP_EBADLOG;  // (the index disagrees with the log)
+    }
+    if (added) *added = (uint32_t)plan.cps.size();
+    if (tombstoned) *tombstoned = (uint32_t)plan.ndel;
+    return CRDT_HIP_OK;
+}
+
 // Wire format (little-endian): magic, version, first_id, n_items, first_del, n_dels,
 // parent[n], origin_right[n], lamport[n], cp[n] (u32), agent[n] (u16, padded to 4), dels[m].
 // Fugue logs write version 2, with bit 31 of cp[k] = side (1: left child of parent[k]).

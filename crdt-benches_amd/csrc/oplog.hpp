@@ -92,6 +92,29 @@ struct PatchRec {
     uint32_t del, ins_len;
 };
 
+// Local edits as positional patches (crdt_hip.h, "local edits"; the device twin is edit.hip).
+// What the checks that need no log leave behind, shared by the host and the device path: per patch
+// its position in the document before the call (old-document coordinates), the range it deletes,
+// and where its codepoints and its deleted ids start in the call's flattened lists.
+struct EditPatch {
+    uint32_t old_pos;  // visible items before the patch in the document before the call
+    uint32_t del;      // items of old visible rank old_pos + 1 .. old_pos + del are deleted
+    uint32_t cp0;      // first of its codepoints in EditPlan::cps (new id = items held + 1 + cp0)
+    uint32_t ncp;      // codepoints it inserts
+    uint32_t del0;     // deleted items of the patches before it
+    uint32_t pad;
+};
+struct EditPlan {
+    std::vector<EditPatch> patch;
+    std::vector<uint32_t> cps;  // every inserted codepoint, patch after patch
+    uint64_t ndel = 0;          // items the call deletes
+};
+// Validates a patch array against a document of `visible` codepoints and `items` items, in the
+// order and with the codes crdt_hip.h states (everything but the lamport bound, which needs the
+// log), and fills the plan.  CRDT_HIP_OK, EINVAL or ERANGE with `err` set.
+int edit_plan(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len, uint64_t visible,
+              uint64_t items, EditPlan& plan, std::string& err);
+
 class OpLog {
 public:
     // ---- SoA (index k holds item id k+1) ----
@@ -170,6 +193,13 @@ public:
     LogMark mark() const;
     int patches_since(const LogMark& m, std::vector<PatchRec>& out, std::vector<uint8_t>& ins,
                       std::string& err) const;
+    // Local edits as a set of positional patches in the patches_since convention (crdt_hip.h,
+    // "local edits"): validated up front (edit_plan, then the lamport bound and the positional
+    // index), and a rejected call changes nothing; then remove + insert per patch, in order, which
+    // is the definition the device path (edit.hip) is held to.  *added: items appended,
+    // *tombstoned: items deleted (either may be null).
+    int apply_patches(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
+                      uint32_t* added, uint32_t* tombstoned, std::string& err);
     // Every item id in document order, tombstones included (RGA pre-order or Fugue in-order): the
     // sibling sort and walk that rebuild_index / rebuild_index_fugue build their index from.
     std::string document_order(std::vector<uint32_t>& order) const;

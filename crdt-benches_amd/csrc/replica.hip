@@ -479,6 +479,7 @@ int replica_copy(Engine& E, const Replica& src, Replica& dst) {
         RCHK(hipGetLastError(), "replica copy");
     }
     dst.n = src.n;
+    dst.agent = src.agent;
     D.fugue = S.fugue;
     dst.vis_cp = src.vis_cp;
     dst.vis_bytes = src.vis_bytes;

@@ -77,6 +77,7 @@ struct Replica {
     bool pending = false;      // a decode was enqueued and its counters not yet applied
     uint64_t gen = 0;          // bumped by every (re)allocation of the replica's device arrays
     uint64_t version = 0;      // bumped by every change of the contents
+    uint16_t agent = 0;        // agent id of the replica's own edits (edit.hip); a clone keeps it
     std::vector<void*> graveyard;  // arrays replaced by a regrow, freed at the next wait
     IncState inc;              // incremental merge state (invalid until the first merge_inc)
 
@@ -230,6 +231,25 @@ int replica_mark(Engine& E, Replica& r, DeviceMark& m);
 int replica_patches_since(Engine& E, Replica& r, const DeviceMark& m, PatchRec* out, size_t cap,
                           size_t* out_n, uint8_t* ins, size_t ins_cap, size_t* out_ins,
                           PatchStats* stats = nullptr);
+
+// Local edits (edit.hip; semantics in crdt_hip.h, host twin OpLog::apply_patches): a set of
+// positional patches in the patches_since convention, resolved against the kept document order and
+// applied as items and tombstones under r.agent.
+struct EditStats {  // what the last device apply_patches observed (crdt_hip_edit_stats)
+    uint64_t patches = 0;     // patches applied
+    uint64_t items = 0;       // items appended
+    uint64_t tombstones = 0;  // items tombstoned
+    uint64_t ranks = 0;       // ranks of the document order streamed (the items held before)
+    uint64_t device_ns = 0;   // summed device time of the call's kernels, the decode of the
+                              //   update they write included (HIP events; not the order update)
+};
+// Validates everything first (EINVAL / ERANGE as OpLog::apply_patches; a rejected call changes
+// nothing), brings r.inc up to date as replica_merge_inc does, resolves the patches in kernels
+// into one wire update in device memory and hands it to replica_decode_enqueue: the replica is
+// left as replica_decode of that update leaves it.  *added / *tombstoned may be null.
+int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, const uint8_t* ins,
+                          size_t ins_len, uint32_t* added, uint32_t* tombstoned,
+                          EditStats* stats = nullptr);
 
 // Incremental merge (incr.hip): the merged text (may be null), its UTF-8 bytes and codepoints;
 // *path = 1 when only the items appended since the previous merge_inc were ranked, 0 for a

@@ -29,6 +29,9 @@
  *                           crdt_hip_replica_mark + crdt_hip_replica_patches_since: what an update,
  *                           a join or a delta changed in the document, as positional edits for an
  *                           editor that keeps a text buffer beside the log ("patches since a mark")
+ *   insert / remove / replace on the device (Upstream for a resident replica)
+ *                        -> crdt_hip_replica_replace / crdt_hip_replica_apply_patches ("local
+ *                           edits"): positions resolved to identities in HIP kernels
  *
  * Conventions
  *   - Every function returns int status: 0 = ok, < 0 = error (CRDT_HIP_E*).  Nothing throws or
@@ -368,6 +371,61 @@ void crdt_hip_mark_free(crdt_hip_mark* m);
 int crdt_hip_oplog_patches_since(crdt_hip_oplog* log, const crdt_hip_mark* m, crdt_hip_patch* out,
                                  size_t cap, size_t* out_n, uint8_t* ins, size_t ins_cap,
                                  size_t* out_ins);
+
+/* ---- local edits: positional patches into a log or a replica ----------------------------------
+ * The inverse of patches_since: a set of positional patches applied as local edits, on the host
+ * (crdt_hip_oplog_apply_patches) or, in HIP kernels, to a replica where it lies
+ * (crdt_hip_replica_apply_patches), under the replica's own agent (crdt_hip_replica_set_agent,
+ * default 0; a clone keeps it).  With it a device replica is a full peer: it edits, syncs and
+ * reports, and needs no host twin (`impl Upstream` for the device replica).
+ *
+ * A patch array reads in the patches_since convention: patch k is
+ * replace(pos..pos + del, ins[ins_off, +ins_len)), applied in array order, pos counted in the
+ * document as the earlier patches of the array left it.  The result is defined by the host: the
+ * log that crdt_hip_oplog_replace, called once per patch in order, produces on a log that holds
+ * the same items and has the same local agent, slot for slot: ids (n + 1 ... in patch order, then
+ * codepoint order), parents, lamports (largest lamport held + 1, + 2, ...), agent, tombstones and
+ * (Fugue) sides.  The device log carries no origin_right, as after a delta.
+ *
+ * Everything is validated before anything changes, and a rejected call changes nothing; n == 0 is
+ * ok and changes nothing.
+ *   CRDT_HIP_EINVAL  a patch with del == 0 and ins_len == 0; patches that are not ascending and
+ *                    non-touching (the rule is pos[k + 1] > pos[k] + codepoints(ins[k]), what
+ *                    patches_since guarantees); a piece [ins_off, ins_off + ins_len) outside
+ *                    `ins`; a piece that is not UTF-8 by the rule of crdt_hip_oplog_insert; a
+ *                    replica of another context
+ *   CRDT_HIP_ERANGE  pos[k] + del[k] beyond the document as the earlier patches left it; an item
+ *                    count that would reach the op-log limit; lamports that would reach
+ *                    0xFFFFFFFF
+ * *added: items appended; *tombstoned: items deleted (either may be NULL).
+ *
+ * The device call checks the arguments on the host against the visible length the replica tracks,
+ * brings the kept document order up to date exactly as crdt_hip_replica_patches_since does, then
+ * counts the visible items per tile of 4,096 ranks, scans the tile counts, and resolves: every
+ * visible item finds its patch by its visible rank, becomes a patch's left neighbour or one of its
+ * deleted items, and one thread per inserted codepoint emits the new item.  The kernels write one
+ * wire update in device memory that the replica's own decoder applies, so a call leaves the
+ * replica as crdt_hip_replica_apply_updates of that update would; the host waits once before the
+ * decode (the largest lamport held and the integrity counts).  No host copy of the replica's
+ * columns is made.  Known cost: a call streams every slot and every rank of the replica, even for
+ * a single keystroke.
+ * crdt_hip_replica_replace is one patch with Upstream::replace's reading (rope.rs:21-32): remove
+ * if end > start, insert if nbytes > 0, nothing otherwise. */
+int crdt_hip_oplog_apply_patches(crdt_hip_oplog* log, const crdt_hip_patch* p, size_t n,
+                                 const uint8_t* ins, size_t ins_len, uint32_t* added,
+                                 uint32_t* tombstoned);
+int crdt_hip_replica_set_agent(crdt_hip_replica* r, uint16_t agent);
+int crdt_hip_replica_apply_patches(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_patch* p,
+                                   size_t n, const uint8_t* ins, size_t ins_len, uint32_t* added,
+                                   uint32_t* tombstoned);
+int crdt_hip_replica_replace(crdt_hip_ctx* ctx, crdt_hip_replica* r, size_t start, size_t end,
+                             const char* utf8, size_t nbytes);
+/* What the context's last crdt_hip_replica_apply_patches observed (each may be NULL): patches
+ * applied, items appended, items tombstoned, ranks of the document order streamed (the items held
+ * before the call), and the summed device time of the call's kernels in ns, the decode of the
+ * update they write included (HIP events; the order update is not included). */
+int crdt_hip_edit_stats(const crdt_hip_ctx* ctx, uint64_t* patches, uint64_t* items,
+                        uint64_t* tombstones, uint64_t* ranks, uint64_t* device_ns);
 
 /* ---- trace loader (crdt-testdata load_testing_data / chars_to_bytes, main.rs:19-23) ---------- */
 int crdt_hip_trace_load(const char* path, crdt_hip_trace** out);
