@@ -52,7 +52,6 @@
 // streaming work however small the delta: what the delta saves is the bytes exchanged.
 #include <algorithm>
 #include <cstring>
-#include <initializer_list>
 #include <vector>
 
 #include "idtab.hpp"
@@ -205,24 +204,11 @@ __global__ __launch_bounds__(kJB) void k_enc_classify(EncArgs a) {
     }
 }
 
-// One workgroup: v[0..m) -> exclusive prefixes; returns the total (in every thread).
-__device__ __forceinline__ uint32_t top_scan(uint32_t* v, uint32_t m, uint32_t* lds) {
-    uint32_t c0 = 0;
-    for (uint32_t base = 0; base < m; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t x = i < m ? v[i] : 0u;
-        uint32_t t0;
-        const uint32_t e0 = block_excl_scan<16>(x, lds, t0);
-        if (i < m) v[i] = c0 + e0;
-        c0 += t0;
-    }
-    return c0;
-}
 __global__ __launch_bounds__(1024) void k_enc_top(EncArgs a) {
     __shared__ uint32_t lds[16];
-    const uint32_t ti = top_scan(a.blk_i, a.nblk, lds);
-    const uint32_t th = top_scan(a.blk_h, a.nblk, lds);
-    (void)top_scan(a.blk_e, a.nblk, lds);
+    const uint32_t ti = (uint32_t)block_scan_counts<1024>(a.blk_i, a.nblk, lds);
+    const uint32_t th = (uint32_t)block_scan_counts<1024>(a.blk_h, a.nblk, lds);
+    (void)block_scan_counts<1024>(a.blk_e, a.nblk, lds);
     if (threadIdx.x == 0) {
         a.ctl[D_ITEMS] = ti;
         a.ctl[D_RANGES] = th;
@@ -333,32 +319,20 @@ __global__ __launch_bounds__(kJB) void k_dl_probe(ApplyArgs a) {
 
 __global__ __launch_bounds__(1024) void k_dl_top(ApplyArgs a) {
     __shared__ uint32_t lds[16];
-    const uint32_t t = top_scan(a.blk, a.nblk, lds);
+    const uint32_t t = (uint32_t)block_scan_counts<1024>(a.blk, a.nblk, lds);
     if (threadIdx.x == 0) a.ctl[D_ADDED] = t;
 }
 
 __global__ __launch_bounds__(kJB) void k_dl_rank(ApplyArgs a) {
-    __shared__ uint32_t lds[kJB / 64];
     const uint32_t i = blockIdx.x * kJB + threadIdx.x;
-    const bool isnew = i < a.n && a.map[i] == kEmpty;
-    uint32_t tot;
-    const uint32_t e = block_excl_scan<kJB / 64>(isnew ? 1u : 0u, lds, tot);
-    if (isnew) a.map[i] = a.nd + 1u + a.blk[blockIdx.x] + e;
+    rank_new(a.map, a.blk, a.nd + 1u, i, i < a.n);
 }
 
 // One workgroup: the range counts -> roff[k] = items of the ranges before k, roff[r] = the total.
 __global__ __launch_bounds__(1024) void k_dl_roff(ApplyArgs a) {
     __shared__ uint32_t lds[16];
-    uint64_t c0 = 0;
-    for (uint32_t base = 0; base < a.r; base += 1024) {
-        const uint32_t k = base + threadIdx.x;
-        const uint32_t x = k < a.r ? a.rcount[k] : 0u;
-        uint32_t t0;
-        const uint32_t e0 = block_excl_scan<16>(x, lds, t0);
-        // (a count so large that a 1024-range sum wraps: the sum differs from the host's total)
-        if (k < a.r) a.roff[k] = (uint32_t)(c0 + e0);
-        c0 += t0;
-    }
+    // (a count so large that a 1024-range sum wraps: the sum differs from the host's total)
+    const uint64_t c0 = block_scan_counts<1024>(a.rcount, a.roff, a.r, lds);
     if (threadIdx.x == 0) {
         a.roff[a.r] = a.total;
         if (c0 != a.total) atomicOr((unsigned long long*)&a.ctl[D_ERR], (unsigned long long)ED_RANGE);
@@ -505,61 +479,6 @@ __global__ __launch_bounds__(kJB) void k_dl_tomb(ApplyArgs a) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-int dfail(Engine& E, const char* what, hipError_t e) {
-    E.err = std::string(what) + ": " + hipGetErrorString(e);
-    (void)hipGetLastError();
-    return CRDT_HIP_EDEVICE;
-}
-
-#define DCHK(expr, what)                                 \
-    do {                                                 \
-        hipError_t _e = (expr);                          \
-        if (_e != hipSuccess) return dfail(E, what, _e); \
-    } while (0)
-
-// A call's transient device arrays, counters and events, released after a wait for the stream.
-struct DeltaScratch {
-    hipStream_t stream = nullptr;
-    std::vector<void*> dev;
-    uint64_t* ctl = nullptr;
-    uint64_t* hctl = nullptr;  // pinned host copy
-    void* hbuf = nullptr;      // pinned staging (state vector entries)
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    uint64_t dev_ns = 0;  // summed device time of the kernel groups
-    template <class T>
-    hipError_t alloc(T** p, uint64_t count) {
-        const hipError_t rc = dalloc(p, count);
-        if (rc == hipSuccess) dev.push_back(*p);
-        return rc;
-    }
-    hipError_t counters() {
-        hipError_t rc = alloc(&ctl, (uint64_t)D_N);
-        if (rc == hipSuccess) rc = pool_alloc(reinterpret_cast<void**>(&hctl), D_N * 8, true);
-        return rc;
-    }
-    hipError_t time_begin() {
-        for (hipEvent_t& e : ev)
-            if (!e) {
-                const hipError_t rc = hipEventCreate(&e);
-                if (rc != hipSuccess) return rc;
-            }
-        return hipEventRecord(ev[0], stream);
-    }
-    hipError_t time_end() { return hipEventRecord(ev[1], stream); }
-    void time_add() {  // (after a wait for the stream)
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) dev_ns += (uint64_t)(ms * 1e6);
-    }
-    ~DeltaScratch() {
-        (void)hipStreamSynchronize(stream);
-        for (void* p : dev) pool_free(p, false, true);
-        if (hctl) pool_free(hctl, true);
-        if (hbuf) pool_free(hbuf, true);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
 int replica_ready(Engine& E, const Replica& r) {
     if (r.pending) {
         E.err = "replica has an unsettled decode";
@@ -606,32 +525,31 @@ int replica_state_vector(Engine& E, const Replica& r, std::vector<SvEntry>& out,
     int rc = replica_ready(E, r);
     if (rc) return rc;
     if (r.n == 0) return CRDT_HIP_OK;
-    DCHK(hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     hipStream_t s = E.stream;
-    DeltaScratch sc;
-    sc.stream = s;
-    DCHK(sc.counters(), "hipMalloc delta counters");
+    CallScratch sc(s);
+    HIPTRY(E, sc.counters(D_N), "hipMalloc delta counters");
     unsigned long long* top = nullptr;
     uint2* ent = nullptr;
-    DCHK(sc.alloc(&top, (uint64_t)kAgents), "hipMalloc state vector table");
-    DCHK(sc.alloc(&ent, (uint64_t)kAgents), "hipMalloc state vector");
+    HIPTRY(E, sc.alloc(&top, (uint64_t)kAgents), "hipMalloc state vector table");
+    HIPTRY(E, sc.alloc(&ent, (uint64_t)kAgents), "hipMalloc state vector");
     uint32_t* present = nullptr;
-    DCHK(sc.alloc(&present, (uint64_t)kAgents / 32), "hipMalloc state vector bits");
-    DCHK(hipMemsetAsync(top, 0, kAgents * 8ull, s), "memset state vector table");
-    DCHK(hipMemsetAsync(present, 0, kAgents / 8, s), "memset state vector bits");
-    DCHK(sc.time_begin(), "delta event");
+    HIPTRY(E, sc.alloc(&present, (uint64_t)kAgents / 32), "hipMalloc state vector bits");
+    HIPTRY(E, hipMemsetAsync(top, 0, kAgents * 8ull, s), "memset state vector table");
+    HIPTRY(E, hipMemsetAsync(present, 0, kAgents / 8, s), "memset state vector bits");
+    HIPTRY(E, sc.time_begin(), "delta event");
     k_dl_init<<<1, 64, 0, s>>>(sc.ctl);
     k_sv_max<<<grid_stride(r.n), kJB, 0, s>>>(r.logs.key, r.n, top, present);
     k_sv_compact<<<1, 1024, 0, s>>>(top, present, ent, sc.ctl);
-    DCHK(hipGetLastError(), "state vector kernels");
-    DCHK(sc.time_end(), "delta event");
-    DCHK(hipMemcpyAsync(sc.hctl, sc.ctl, D_N * 8, hipMemcpyDeviceToHost, s), "copy delta counters");
-    DCHK(hipStreamSynchronize(s), "delta sync");
+    HIPTRY(E, hipGetLastError(), "state vector kernels");
+    HIPTRY(E, sc.time_end(), "delta event");
+    HIPTRY(E, hipMemcpyAsync(sc.hctl, sc.ctl, D_N * 8, hipMemcpyDeviceToHost, s), "copy delta counters");
+    HIPTRY(E, hipStreamSynchronize(s), "delta sync");
     sc.time_add();
     const uint64_t m = std::min<uint64_t>(sc.hctl[D_SV_N], kAgents);
     out.resize(m);
     static_assert(sizeof(SvEntry) == sizeof(uint2), "state vector entry layout");
-    if (m) DCHK(hipMemcpy(out.data(), ent, m * sizeof(SvEntry), hipMemcpyDeviceToHost), "copy state vector");
+    if (m) HIPTRY(E, hipMemcpy(out.data(), ent, m * sizeof(SvEntry), hipMemcpyDeviceToHost), "copy state vector");
     if (stats) stats->device_ns = sc.dev_ns;
     return CRDT_HIP_OK;
 }
@@ -649,13 +567,12 @@ int replica_encode_diff(Engine& E, const Replica& r, const SvEntry* sv, size_t n
     const bool fugue = r.logs.fugue;
     const uint32_t n = r.n;
     uint32_t ni = 0, nr = 0;
-    DCHK(hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     hipStream_t s = E.stream;
-    DeltaScratch sc;
-    sc.stream = s;
+    CallScratch sc(s);
     EncArgs a{};
     if (n) {
-        DCHK(sc.counters(), "hipMalloc delta counters");
+        HIPTRY(E, sc.counters(D_N), "hipMalloc delta counters");
         unsigned long long* bound = nullptr;
         uint2* dsv = nullptr;
         a.par = r.logs.parent;
@@ -664,24 +581,24 @@ int replica_encode_diff(Engine& E, const Replica& r, const SvEntry* sv, size_t n
         a.n = n;
         a.nblk = grid_for(n, kJB);
         a.ctl = sc.ctl;
-        DCHK(sc.alloc(&bound, (uint64_t)kAgents), "hipMalloc bound table");
-        DCHK(sc.alloc(&dsv, (uint64_t)nsv), "hipMalloc state vector");
-        DCHK(sc.alloc(&a.flag, (uint64_t)n), "hipMalloc delta flags");
-        DCHK(sc.alloc(&a.blk_i, (uint64_t)a.nblk), "hipMalloc delta blocks");
-        DCHK(sc.alloc(&a.blk_h, (uint64_t)a.nblk), "hipMalloc delta blocks");
-        DCHK(sc.alloc(&a.blk_e, (uint64_t)a.nblk), "hipMalloc delta blocks");
+        HIPTRY(E, sc.alloc(&bound, (uint64_t)kAgents), "hipMalloc bound table");
+        HIPTRY(E, sc.alloc(&dsv, (uint64_t)nsv), "hipMalloc state vector");
+        HIPTRY(E, sc.alloc(&a.flag, (uint64_t)n), "hipMalloc delta flags");
+        HIPTRY(E, sc.alloc(&a.blk_i, (uint64_t)a.nblk), "hipMalloc delta blocks");
+        HIPTRY(E, sc.alloc(&a.blk_h, (uint64_t)a.nblk), "hipMalloc delta blocks");
+        HIPTRY(E, sc.alloc(&a.blk_e, (uint64_t)a.nblk), "hipMalloc delta blocks");
         a.bound = bound;
-        DCHK(hipMemsetAsync(bound, 0, kAgents * 8ull, s), "memset bound table");
-        if (nsv) DCHK(hipMemcpyAsync(dsv, sv, nsv * sizeof(SvEntry), hipMemcpyHostToDevice, s), "upload state vector");
-        DCHK(sc.time_begin(), "delta event");
+        HIPTRY(E, hipMemsetAsync(bound, 0, kAgents * 8ull, s), "memset bound table");
+        if (nsv) HIPTRY(E, hipMemcpyAsync(dsv, sv, nsv * sizeof(SvEntry), hipMemcpyHostToDevice, s), "upload state vector");
+        HIPTRY(E, sc.time_begin(), "delta event");
         k_dl_init<<<1, 64, 0, s>>>(sc.ctl);
         if (nsv) k_enc_bound<<<grid_for(nsv, kJB), kJB, 0, s>>>(dsv, (uint32_t)nsv, bound);
         if (fugue) enc_launch<true>(a, s);
         else enc_launch<false>(a, s);
-        DCHK(hipGetLastError(), "delta classify kernels");
-        DCHK(sc.time_end(), "delta event");
-        DCHK(hipMemcpyAsync(sc.hctl, sc.ctl, D_N * 8, hipMemcpyDeviceToHost, s), "copy delta counters");
-        DCHK(hipStreamSynchronize(s), "delta sync");  // the one wait: the sizes
+        HIPTRY(E, hipGetLastError(), "delta classify kernels");
+        HIPTRY(E, sc.time_end(), "delta event");
+        HIPTRY(E, hipMemcpyAsync(sc.hctl, sc.ctl, D_N * 8, hipMemcpyDeviceToHost, s), "copy delta counters");
+        HIPTRY(E, hipStreamSynchronize(s), "delta sync");  // the one wait: the sizes
         sc.time_add();
         ni = (uint32_t)std::min<uint64_t>(sc.hctl[D_ITEMS], n);
         nr = (uint32_t)std::min<uint64_t>(sc.hctl[D_RANGES], n);
@@ -706,22 +623,22 @@ int replica_encode_diff(Engine& E, const Replica& r, const SvEntry* sv, size_t n
     if (bytes == 16) return CRDT_HIP_OK;
     // the columns, in wire order behind the header (16 + 16 ni + 8 nr: every u64 column 8-aligned)
     uint8_t* out = nullptr;
-    DCHK(sc.alloc(&out, bytes - 16), "hipMalloc delta");
-    DCHK(sc.alloc(&a.hslot, (uint64_t)nr), "hipMalloc delta ranges");
-    DCHK(sc.alloc(&a.eslot, (uint64_t)nr), "hipMalloc delta ranges");
+    HIPTRY(E, sc.alloc(&out, bytes - 16), "hipMalloc delta");
+    HIPTRY(E, sc.alloc(&a.hslot, (uint64_t)nr), "hipMalloc delta ranges");
+    HIPTRY(E, sc.alloc(&a.eslot, (uint64_t)nr), "hipMalloc delta ranges");
     a.okey = reinterpret_cast<uint64_t*>(out);
     a.opkey = a.okey + ni;
     a.orkey = a.opkey + ni;
     a.ocp = reinterpret_cast<uint32_t*>(a.orkey + nr);
     a.orcount = a.ocp + ni;
-    DCHK(sc.time_begin(), "delta event");
+    HIPTRY(E, sc.time_begin(), "delta event");
     if (fugue) k_enc_write<true><<<a.nblk, kJB, 0, s>>>(a, ni, nr);
     else k_enc_write<false><<<a.nblk, kJB, 0, s>>>(a, ni, nr);
     if (nr) k_enc_counts<<<grid_for(nr, kJB), kJB, 0, s>>>(a, nr);
-    DCHK(hipGetLastError(), "delta write kernels");
-    DCHK(sc.time_end(), "delta event");
-    DCHK(hipMemcpyAsync(buf + 16, out, bytes - 16, hipMemcpyDeviceToHost, s), "copy delta");
-    DCHK(hipStreamSynchronize(s), "delta sync");
+    HIPTRY(E, hipGetLastError(), "delta write kernels");
+    HIPTRY(E, sc.time_end(), "delta event");
+    HIPTRY(E, hipMemcpyAsync(buf + 16, out, bytes - 16, hipMemcpyDeviceToHost, s), "copy delta");
+    HIPTRY(E, hipStreamSynchronize(s), "delta sync");
     sc.time_add();
     if (stats) stats->device_ns = sc.dev_ns;
     return CRDT_HIP_OK;
@@ -733,7 +650,7 @@ int replica_apply_diff(Engine& E, Replica& dst, const uint8_t* buf, size_t len, 
     if (tombstoned) *tombstoned = 0;
     if (stats) *stats = DeltaStats{};
     const bool fugue = dst.logs.fugue;
-    DCHK(hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     int rc = replica_settle(E, dst);
     if (rc) return rc;
     const uint32_t nd = dst.n;
@@ -749,24 +666,23 @@ int replica_apply_diff(Engine& E, Replica& dst, const uint8_t* buf, size_t len, 
     rc = replica_reserve(E, dst, (uint64_t)nd + f.n);
     if (rc) return rc;
     hipStream_t s = E.stream;
-    DeltaScratch sc;
-    sc.stream = s;
-    DCHK(sc.counters(), "hipMalloc delta counters");
+    CallScratch sc(s);
+    HIPTRY(E, sc.counters(D_N), "hipMalloc delta counters");
     uint8_t* dbuf = nullptr;
     ApplyArgs a{};
     const uint64_t dcap = pow2_at_least(2ull * nd), icap = pow2_at_least(2ull * f.n);
     a.nblk = grid_for(f.n, kJB);
-    DCHK(sc.alloc(&dbuf, (uint64_t)len), "hipMalloc delta");
-    DCHK(sc.alloc(&a.dtab, dcap), "hipMalloc delta table");
-    DCHK(sc.alloc(&a.itab, icap), "hipMalloc delta table");
-    DCHK(sc.alloc(&a.map, (uint64_t)f.n), "hipMalloc delta map");
-    DCHK(sc.alloc(&a.tpar, (uint64_t)f.n), "hipMalloc delta map");
-    DCHK(sc.alloc(&a.blk, (uint64_t)a.nblk), "hipMalloc delta blocks");
-    DCHK(sc.alloc(&a.roff, (uint64_t)f.r + 1), "hipMalloc delta ranges");
-    DCHK(sc.alloc(&a.rslot, f.range_items), "hipMalloc delta ranges");
-    DCHK(hipMemcpyAsync(dbuf, buf, len, hipMemcpyHostToDevice, s), "upload delta");
-    DCHK(hipMemsetAsync(a.dtab, 0xFF, dcap * 4, s), "memset delta table");
-    DCHK(hipMemsetAsync(a.itab, 0xFF, icap * 4, s), "memset delta table");
+    HIPTRY(E, sc.alloc(&dbuf, (uint64_t)len), "hipMalloc delta");
+    HIPTRY(E, sc.alloc(&a.dtab, dcap), "hipMalloc delta table");
+    HIPTRY(E, sc.alloc(&a.itab, icap), "hipMalloc delta table");
+    HIPTRY(E, sc.alloc(&a.map, (uint64_t)f.n), "hipMalloc delta map");
+    HIPTRY(E, sc.alloc(&a.tpar, (uint64_t)f.n), "hipMalloc delta map");
+    HIPTRY(E, sc.alloc(&a.blk, (uint64_t)a.nblk), "hipMalloc delta blocks");
+    HIPTRY(E, sc.alloc(&a.roff, (uint64_t)f.r + 1), "hipMalloc delta ranges");
+    HIPTRY(E, sc.alloc(&a.rslot, f.range_items), "hipMalloc delta ranges");
+    HIPTRY(E, hipMemcpyAsync(dbuf, buf, len, hipMemcpyHostToDevice, s), "upload delta");
+    HIPTRY(E, hipMemsetAsync(a.dtab, 0xFF, dcap * 4, s), "memset delta table");
+    HIPTRY(E, hipMemsetAsync(a.itab, 0xFF, icap * 4, s), "memset delta table");
     a.dpar = dst.logs.parent;
     a.dkey = dst.logs.key;
     a.dcp = dst.logs.cp;
@@ -783,14 +699,14 @@ int replica_apply_diff(Engine& E, Replica& dst, const uint8_t* buf, size_t len, 
     a.dmask = (uint32_t)(dcap - 1);
     a.imask = (uint32_t)(icap - 1);
     a.ctl = sc.ctl;
-    DCHK(sc.time_begin(), "delta event");
+    HIPTRY(E, sc.time_begin(), "delta event");
     k_dl_init<<<1, 64, 0, s>>>(sc.ctl);
     if (fugue) apply_launch<true>(a, s);
     else apply_launch<false>(a, s);
-    DCHK(hipGetLastError(), "delta apply kernels");
-    DCHK(sc.time_end(), "delta event");
-    DCHK(hipMemcpyAsync(sc.hctl, sc.ctl, D_N * 8, hipMemcpyDeviceToHost, s), "copy delta counters");
-    DCHK(hipStreamSynchronize(s), "delta sync");
+    HIPTRY(E, hipGetLastError(), "delta apply kernels");
+    HIPTRY(E, sc.time_end(), "delta event");
+    HIPTRY(E, hipMemcpyAsync(sc.hctl, sc.ctl, D_N * 8, hipMemcpyDeviceToHost, s), "copy delta counters");
+    HIPTRY(E, hipStreamSynchronize(s), "delta sync");
     sc.time_add();
     const uint64_t* c = sc.hctl;
     if (stats) {

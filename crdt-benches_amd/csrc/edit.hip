@@ -17,7 +17,7 @@
 //                   plane (atomicOr of the parent's bit for every item that is no left child;
 //                   slot 0 included).  The plane is rebuilt by every call: it is a function of two
 //                   columns and costs one pass that is needed for the lamport anyway
-//   k_edit_count    a workgroup per tile of kPatchTile = 4,096 consecutive ranks, four ranks per
+//   k_edit_count    a workgroup per tile of kOrderTile = 4,096 consecutive ranks, four ranks per
 //                   thread (one 16-byte load of the order), the codepoint word gathered per rank:
 //                   the tile's visible items
 //   k_edit_top      one workgroup scans the tile counts
@@ -52,18 +52,13 @@
 
 #include "idtab.hpp"
 #include "oplog.hpp"
+#include "order.hpp"
 #include "replica.hpp"
 #include "util.hpp"
 #include "wave.hpp"
 
 namespace crdt {
 namespace {
-
-constexpr uint32_t kET = 1024;                       // threads of a tile's workgroup
-constexpr uint32_t kEPerThread = kPatchTile / kET;   // consecutive ranks per thread
-static_assert(kEPerThread == 4, "a thread loads its ranks as one uint4");
-constexpr uint32_t kEW = kET / 64;                   // waves per workgroup
-constexpr int kETop = 256;                           // threads of k_edit_top
 
 // device counters (u64)
 enum ECtl { E_ERR = 0, E_MAXLAM, E_VIS, E_LEFTS, E_DELS, E_N };
@@ -130,60 +125,37 @@ __global__ __launch_bounds__(kJB) void k_edit_slots(EditArgs a) {
 
 // The slots of the thread's four ranks k0..k0 + 3 and whether each holds a visible item (ranks
 // past n, rank 0, tombstones and slots that are no item: not visible).
-__device__ __forceinline__ void edit_load(const EditArgs& a, uint64_t k0, uint32_t sl[kEPerThread],
-                                          bool vis[kEPerThread], uint64_t& err) {
-    if (k0 + kEPerThread - 1 <= a.n) {
-        const uint4 v = *reinterpret_cast<const uint4*>(a.seq + k0);  // (k0 is a multiple of 4)
-        sl[0] = v.x;
-        sl[1] = v.y;
-        sl[2] = v.z;
-        sl[3] = v.w;
-    } else {
+__device__ __forceinline__ void edit_load(const EditArgs& a, uint64_t k0, uint32_t sl[kOrdPer],
+                                          bool vis[kOrdPer], uint64_t& err) {
 #pragma unroll
-        for (uint32_t j = 0; j < kEPerThread; ++j) sl[j] = k0 + j <= a.n ? a.seq[k0 + j] : 0u;
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < kEPerThread; ++j) {
+    for (uint32_t j = 0; j < kOrdPer; ++j) {
+        sl[j] = 0;
         vis[j] = false;
-        if (k0 + j == 0 || k0 + j > a.n) {
-            sl[j] = 0;
-            continue;
-        }
-        if (sl[j] == 0 || sl[j] > a.n) {
-            err |= EE_SLOT;
-            sl[j] = 0;
-            continue;
-        }
-        vis[j] = !(cp3_get(a.cp, sl[j]) & kDelBit);
     }
+    order_load4(a.seq, a.cp, a.n, k0, err, EE_SLOT, [&](uint32_t j, uint32_t s, uint32_t c) {
+        sl[j] = s;
+        vis[j] = !(c & kDelBit);
+    });
 }
 
-__global__ __launch_bounds__(kET) void k_edit_count(EditArgs a) {
-    __shared__ uint32_t red[kEW];
-    const uint64_t k0 = (uint64_t)blockIdx.x * kPatchTile + (uint64_t)threadIdx.x * kEPerThread;
-    uint32_t sl[kEPerThread];
-    bool vis[kEPerThread];
+__global__ __launch_bounds__(kOrdT) void k_edit_count(EditArgs a) {
+    __shared__ uint32_t red[kOrdW];
+    const uint64_t k0 = (uint64_t)blockIdx.x * kOrderTile + (uint64_t)threadIdx.x * kOrdPer;
+    uint32_t sl[kOrdPer];
+    bool vis[kOrdPer];
     uint64_t err = 0;
     edit_load(a, k0, sl, vis, err);
     ctl_or(&a.ctl[E_ERR], err);
     uint32_t c = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < kEPerThread; ++j) c += vis[j] ? 1u : 0u;
-    const uint32_t t = block_sum_t0<kEW>(c, red);
+    for (uint32_t j = 0; j < kOrdPer; ++j) c += vis[j] ? 1u : 0u;
+    const uint32_t t = block_sum_t0<kOrdW>(c, red);
     if (threadIdx.x == 0 && blockIdx.x < a.ntiles) a.tcount[blockIdx.x] = t;
 }
 
-__global__ __launch_bounds__(kETop) void k_edit_top(EditArgs a) {
-    __shared__ uint32_t lds[kETop / 64];
-    uint64_t c = 0;
-    for (uint32_t base = 0; base < a.ntiles; base += kETop) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t x = i < a.ntiles ? a.tcount[i] : 0u;
-        uint32_t tot;
-        const uint32_t e = block_excl_scan<kETop / 64>(x, lds, tot);
-        if (i < a.ntiles) a.tcount[i] = (uint32_t)c + e;  // (at most n < 2^31 visible items)
-        c += tot;
-    }
+__global__ __launch_bounds__(kOrdTop) void k_edit_top(EditArgs a) {
+    __shared__ uint32_t lds[kOrdTop / 64];
+    const uint64_t c = block_scan_counts<kOrdTop>(a.tcount, a.ntiles, lds);  // (at most n < 2^31)
     if (threadIdx.x == 0) a.ctl[E_VIS] = c;
 }
 
@@ -199,23 +171,23 @@ __device__ __forceinline__ uint32_t edit_find(const EditPatch* tab, uint32_t np,
     return lo;
 }
 
-__global__ __launch_bounds__(kET) void k_edit_resolve(EditArgs a) {
-    __shared__ uint32_t lds[kEW];
+__global__ __launch_bounds__(kOrdT) void k_edit_resolve(EditArgs a) {
+    __shared__ uint32_t lds[kOrdW];
     if (blockIdx.x >= a.ntiles) return;
-    const uint64_t k0 = (uint64_t)blockIdx.x * kPatchTile + (uint64_t)threadIdx.x * kEPerThread;
-    uint32_t sl[kEPerThread];
-    bool vis[kEPerThread];
+    const uint64_t k0 = (uint64_t)blockIdx.x * kOrderTile + (uint64_t)threadIdx.x * kOrdPer;
+    uint32_t sl[kOrdPer];
+    bool vis[kOrdPer];
     uint64_t err = 0;
     edit_load(a, k0, sl, vis, err);  // (k_edit_count reported any bad slot)
     uint32_t c = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < kEPerThread; ++j) c += vis[j] ? 1u : 0u;
+    for (uint32_t j = 0; j < kOrdPer; ++j) c += vis[j] ? 1u : 0u;
     uint32_t tot;
-    uint32_t v = a.tcount[blockIdx.x] + block_excl_scan<kEW>(c, lds, tot);  // visible before
+    uint32_t v = a.tcount[blockIdx.x] + block_excl_scan<kOrdW>(c, lds, tot);  // visible before
     uint32_t lefts = 0, dels = 0;
     const uint64_t dbase = wire_dels(a);
 #pragma unroll
-    for (uint32_t j = 0; j < kEPerThread; ++j) {
+    for (uint32_t j = 0; j < kOrdPer; ++j) {
         const uint64_t rank = k0 + j;
         if (!vis[j] && rank != 0) continue;
         if (vis[j]) ++v;  // this item's visible rank (the document start: 0)
@@ -245,7 +217,7 @@ __global__ __launch_bounds__(kET) void k_edit_resolve(EditArgs a) {
         }
     }
     ctl_or(&a.ctl[E_ERR], err);
-    const uint32_t s0 = block_sum_t0<kEW>(lefts, lds), s1 = block_sum_t0<kEW>(dels, lds);
+    const uint32_t s0 = block_sum_t0<kOrdW>(lefts, lds), s1 = block_sum_t0<kOrdW>(dels, lds);
     if (threadIdx.x == 0) {
         if (s0) atomicAdd((unsigned long long*)&a.ctl[E_LEFTS], (unsigned long long)s0);
         if (s1) atomicAdd((unsigned long long*)&a.ctl[E_DELS], (unsigned long long)s1);
@@ -313,61 +285,15 @@ __global__ __launch_bounds__(kJB) void k_edit_emit(EditArgs a) {
     reinterpret_cast<uint16_t*>(w + 4ull * a.ncp)[j] = (uint16_t)a.agent;
 }
 
-// ---- host side ---------------------------------------------------------------------------------
-int efail(Engine& E, const char* what, hipError_t e) {
-    E.err = std::string(what) + ": " + hipGetErrorString(e);
-    (void)hipGetLastError();
-    return CRDT_HIP_EDEVICE;
-}
-#define ECHK(expr, what)                                 \
-    do {                                                 \
-        hipError_t _e = (expr);                          \
-        if (_e != hipSuccess) return efail(E, what, _e); \
-    } while (0)
-
-// A call's transient device arrays, counters and events, released after a wait for the stream.
-struct EditScratch {
-    hipStream_t stream = nullptr;
-    std::vector<void*> dev;
-    uint64_t* hctl = nullptr;  // pinned host copy of the counters
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    uint64_t dev_ns = 0;
-    template <class T>
-    hipError_t alloc(T** p, uint64_t count) {
-        const hipError_t rc = dalloc(p, count);
-        if (rc == hipSuccess) dev.push_back(*p);
-        return rc;
-    }
-    hipError_t time_begin() {
-        for (hipEvent_t& e : ev)
-            if (!e) {
-                const hipError_t rc = hipEventCreate(&e);
-                if (rc != hipSuccess) return rc;
-            }
-        return hipEventRecord(ev[0], stream);
-    }
-    hipError_t time_end() { return hipEventRecord(ev[1], stream); }
-    void time_add() {  // (after a wait for the stream)
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) dev_ns += (uint64_t)(ms * 1e6);
-    }
-    ~EditScratch() {
-        (void)hipStreamSynchronize(stream);
-        for (void* p : dev) pool_free(p, false, true);
-        if (hctl) pool_free(hctl, true);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
 }  // namespace
 
+// ---- host side ---------------------------------------------------------------------------------
 int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, const uint8_t* ins,
                           size_t ins_len, uint32_t* added, uint32_t* tombstoned, EditStats* stats) {
     if (stats) *stats = EditStats{};
     if (added) *added = 0;
     if (tombstoned) *tombstoned = 0;
-    ECHK(hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     int rc = replica_settle(E, r);
     if (rc) return rc;
     if (n == 0) return CRDT_HIP_OK;
@@ -386,28 +312,15 @@ int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, co
         return CRDT_HIP_ERANGE;
     }
     const bool empty = r.n == 0;
-    if (!empty) {
-        // the document order of every item held, as a merge_inc leaves it
-        rc = replica_merge_inc(E, r, nullptr, nullptr, nullptr, nullptr);
-        if (rc) return rc;
-        const IncState& inc = r.inc;
-        if (!inc.valid || inc.n != r.n || inc.cap < (uint64_t)r.n + 1 ||
-            (uint64_t)r.n + 1 > r.logs.cap_slots) {
-            E.err = "edit: the kept document order does not cover the replica";
-            return CRDT_HIP_EBADLOG;
-        }
-    }
+    EditArgs a{};  // (an empty replica has no order: seq null, no tiles)
+    if (!empty && (rc = replica_kept_order(E, r, "edit", &a.seq, &a.ntiles))) return rc;
     hipStream_t s = E.stream;
-    EditScratch sc;
-    sc.stream = s;
-    EditArgs a{};
-    a.seq = empty ? nullptr : r.inc.seq[r.inc.cur];
+    CallScratch sc(s);
     a.cp = r.logs.cp;
     a.key = r.logs.key;
     a.parent = r.logs.parent;
     a.n = r.n;
     a.fugue = r.logs.fugue ? 1u : 0u;
-    a.ntiles = empty ? 0u : (uint32_t)(((uint64_t)r.n + 1 + kPatchTile - 1) / kPatchTile);  // ranks 0..n
     a.np = (uint32_t)np;
     a.ncp = (uint32_t)ncp;
     a.ndel = (uint32_t)ndel;
@@ -416,38 +329,38 @@ int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, co
     const uint64_t hasr_words = ((uint64_t)r.n + 32) / 32;
     EditPatch* tab = nullptr;
     uint32_t* cps = nullptr;
-    ECHK(sc.alloc(&a.ctl, (uint64_t)E_N), "hipMalloc edit counters");
-    ECHK(pool_alloc(reinterpret_cast<void**>(&sc.hctl), E_N * 8, true), "hipHostMalloc edit counters");
-    ECHK(sc.alloc(&a.tcount, (uint64_t)a.ntiles), "hipMalloc edit tiles");
-    ECHK(sc.alloc(&a.hasr, hasr_words), "hipMalloc edit right-child bits");
-    ECHK(sc.alloc(&tab, np), "hipMalloc edit patches");
-    ECHK(sc.alloc(&a.left, np), "hipMalloc edit anchors");
-    ECHK(sc.alloc(&a.succ, np), "hipMalloc edit anchors");
-    ECHK(sc.alloc(&cps, ncp), "hipMalloc edit codepoints");
-    ECHK(sc.alloc(&a.wire, words), "hipMalloc edit update");
-    ECHK(sc.alloc(&a.woff, 2), "hipMalloc edit update");
+    HIPTRY(E, sc.counters(E_N), "hipMalloc edit counters");
+    a.ctl = sc.ctl;
+    HIPTRY(E, sc.alloc(&a.tcount, (uint64_t)a.ntiles), "hipMalloc edit tiles");
+    HIPTRY(E, sc.alloc(&a.hasr, hasr_words), "hipMalloc edit right-child bits");
+    HIPTRY(E, sc.alloc(&tab, np), "hipMalloc edit patches");
+    HIPTRY(E, sc.alloc(&a.left, np), "hipMalloc edit anchors");
+    HIPTRY(E, sc.alloc(&a.succ, np), "hipMalloc edit anchors");
+    HIPTRY(E, sc.alloc(&cps, ncp), "hipMalloc edit codepoints");
+    HIPTRY(E, sc.alloc(&a.wire, words), "hipMalloc edit update");
+    HIPTRY(E, sc.alloc(&a.woff, 2), "hipMalloc edit update");
     a.tab = tab;
     a.cps = cps;
     // (plan outlives the wait below, so the uploads may read it until then)
-    ECHK(hipMemcpyAsync(tab, plan.patch.data(), np * sizeof(EditPatch), hipMemcpyHostToDevice, s),
-         "upload edit patches");
-    if (ncp) ECHK(hipMemcpyAsync(cps, plan.cps.data(), ncp * 4, hipMemcpyHostToDevice, s), "upload edit text");
-    ECHK(sc.time_begin(), "edit event");
+    HIPTRY(E, hipMemcpyAsync(tab, plan.patch.data(), np * sizeof(EditPatch), hipMemcpyHostToDevice, s),
+              "upload edit patches");
+    if (ncp) HIPTRY(E, hipMemcpyAsync(cps, plan.cps.data(), ncp * 4, hipMemcpyHostToDevice, s), "upload edit text");
+    HIPTRY(E, sc.time_begin(), "edit event");
     k_edit_init<<<grid_for(std::max<uint64_t>(np, E_N), kJB), kJB, 0, s>>>(a, empty ? 1u : 0u);
     if (!empty) {
-        if (a.fugue) ECHK(hipMemsetAsync(a.hasr, 0, hasr_words * 4, s), "clear right-child bits");
+        if (a.fugue) HIPTRY(E, hipMemsetAsync(a.hasr, 0, hasr_words * 4, s), "clear right-child bits");
         k_edit_slots<<<grid_stride(r.n), kJB, 0, s>>>(a);
-        k_edit_count<<<a.ntiles, kET, 0, s>>>(a);
-        k_edit_top<<<1, kETop, 0, s>>>(a);
-        k_edit_resolve<<<a.ntiles, kET, 0, s>>>(a);
+        k_edit_count<<<a.ntiles, kOrdT, 0, s>>>(a);
+        k_edit_top<<<1, kOrdTop, 0, s>>>(a);
+        k_edit_resolve<<<a.ntiles, kOrdT, 0, s>>>(a);
     } else if (a.fugue) {
-        ECHK(hipMemsetAsync(a.hasr, 0, hasr_words * 4, s), "clear right-child bits");
+        HIPTRY(E, hipMemsetAsync(a.hasr, 0, hasr_words * 4, s), "clear right-child bits");
     }
     k_edit_emit<<<grid_for(std::max<uint64_t>(ncp, 1), kJB), kJB, 0, s>>>(a);
-    ECHK(hipGetLastError(), "edit kernels");
-    ECHK(sc.time_end(), "edit event");
-    ECHK(hipMemcpyAsync(sc.hctl, a.ctl, E_N * 8, hipMemcpyDeviceToHost, s), "copy edit counters");
-    ECHK(hipStreamSynchronize(s), "edit sync");  // the one wait before anything changes
+    HIPTRY(E, hipGetLastError(), "edit kernels");
+    HIPTRY(E, sc.time_end(), "edit event");
+    HIPTRY(E, hipMemcpyAsync(sc.hctl, a.ctl, E_N * 8, hipMemcpyDeviceToHost, s), "copy edit counters");
+    HIPTRY(E, hipStreamSynchronize(s), "edit sync");  // the one wait before anything changes
     sc.time_add();
     const uint64_t* c = sc.hctl;
     if (c[E_ERR]) {
@@ -472,11 +385,11 @@ int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, co
     // the update is whole and checked: the decode applies it (and validates it once more)
     const uint32_t n0 = r.n;
     const uint64_t vis0 = r.vis_cp;
-    ECHK(sc.time_begin(), "edit event");
+    HIPTRY(E, sc.time_begin(), "edit event");
     rc = replica_decode_enqueue(E, r, reinterpret_cast<const uint8_t*>(a.wire), words * 4, a.woff, 1,
                                 true, ncp ? (uint32_t)(n0 + ncp) : 0u, true);
     if (rc) return rc;
-    ECHK(sc.time_end(), "edit event");
+    HIPTRY(E, sc.time_end(), "edit event");
     rc = replica_settle(E, r);
     if (rc) return rc;
     sc.time_add();

@@ -228,6 +228,8 @@ public:
     uint32_t l1_group = 0;
     uint32_t rs_digit_bits = 0;  // sort A's digit width: 0 = 10 bits where that saves a pass, else 8
     std::string err;
+    // err = "<what>: <the HIP error>", the sticky HIP error cleared; returns CRDT_HIP_EDEVICE
+    int fail(const char* what, hipError_t e);
 
     // Plan docs into waves and (re)allocate `L`'s arrays for them (contents undefined).
     // brk (optional, per document): 1 = start a new wave at this document
@@ -463,7 +465,13 @@ private:
                  std::vector<uint32_t>& stage_launches, bool force_global = false);
     void collect(const DeviceLogs& L, uint32_t wi, uint64_t* digests, uint64_t* lens,
                  uint64_t* cps, uint64_t& text_bytes) const;
-    int fail(const char* what, hipError_t e);
 };
+
+// In a function that returns a CRDT_HIP_* code: a HIP error ends it through E.fail.
+#define HIPTRY(E, expr, what)                              \
+    do {                                                   \
+        hipError_t _e = (expr);                            \
+        if (_e != hipSuccess) return (E).fail(what, _e);   \
+    } while (0)
 
 }  // namespace crdt

@@ -1,7 +1,8 @@
 // idtab.hpp — what the kernels that name items by identity share (join.hip, delta.hip): the
 // identity of a key word, the open-addressing identity table (u32 entries claimed by atomicCAS,
-// identity equality by gathering the key column), and the block reductions that keep device
-// counters to one atomic per block.  Header-only, internal linkage.
+// identity equality by gathering the key column) and the ids of the items new to dst; and, for
+// patch.hip and edit.hip too, the block reductions that keep device counters to one atomic per
+// block.  Header-only, internal linkage.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -92,6 +93,18 @@ __device__ __forceinline__ uint32_t tab_find(const uint32_t* tab, uint32_t mask,
         h = (h + 1u) & mask;
     }
     return kEmpty;
+}
+
+// The items new to dst (map[i] == kEmpty; `in`: i is an item) take the ids base + their rank
+// among the new items, in index order.  blk: the exclusive prefixes of the blocks' counts of new
+// items.  Called by every thread of a block of kJB.
+__device__ __forceinline__ void rank_new(uint32_t* map, const uint32_t* blk, uint32_t base, uint64_t i,
+                                         bool in) {
+    __shared__ uint32_t lds[kJB / 64];
+    const bool isnew = in && map[i] == kEmpty;
+    uint32_t tot;
+    const uint32_t e = block_excl_scan<kJB / 64>(isnew ? 1u : 0u, lds, tot);
+    if (isnew) map[i] = base + blk[blockIdx.x] + e;
 }
 
 // Grid of a grid-stride kernel over n slots: four slots per thread (a quarter of the counter

@@ -39,6 +39,7 @@
 #include <cstring>
 
 #include "engine.hpp"
+#include "order.hpp"
 #include "replica.hpp"
 #include "util.hpp"
 #include "wave.hpp"
@@ -869,17 +870,6 @@ __global__ __launch_bounds__(256) void k_inc_maxkey(const uint64_t* key, uint32_
         atomicMax(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)mx);
 }
 
-int ifail(Engine& E, const char* what, hipError_t e) {
-    E.err = std::string(what) + ": " + hipGetErrorString(e);
-    (void)hipGetLastError();
-    return CRDT_HIP_EDEVICE;
-}
-#define ICHK(expr, what)                                 \
-    do {                                                 \
-        hipError_t _e = (expr);                          \
-        if (_e != hipSuccess) return ifail(E, what, _e); \
-    } while (0)
-
 hipError_t inc_setup() {
     static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_inc),
                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -920,7 +910,7 @@ int inc_reserve(Engine& E, IncState& s, uint64_t items, uint64_t bytes) {
             dfree(r0);
             dfree(r1);
             s.valid = false;
-            return ifail(E, "incremental order arrays", e);
+            return E.fail("incremental order arrays", e);
         }
         // (Fugue) the left-child bits, kept too
         uint32_t* h0 = nullptr;
@@ -937,7 +927,7 @@ int inc_reserve(Engine& E, IncState& s, uint64_t items, uint64_t bytes) {
             dfree(r1);
             dfree(h0);
             s.valid = false;
-            return ifail(E, "incremental left-child bits", e);
+            return E.fail("incremental left-child bits", e);
         }
         dfree(s.seq[0]);
         dfree(s.seq[1]);
@@ -958,29 +948,29 @@ int inc_reserve(Engine& E, IncState& s, uint64_t items, uint64_t bytes) {
         dfree(s.lb_agg);
         dfree(s.lb_inc);
         s.lb_cap = 0;
-        ICHK(dalloc(&s.lb_flag, ntiles), "hipMalloc look-back");
-        ICHK(dalloc(&s.lb_agg, ntiles), "hipMalloc look-back");
-        ICHK(dalloc(&s.lb_inc, ntiles), "hipMalloc look-back");
-        ICHK(hipMemsetAsync(s.lb_flag, 0, ntiles * 4, E.stream), "clear look-back");
+        HIPTRY(E, dalloc(&s.lb_flag, ntiles), "hipMalloc look-back");
+        HIPTRY(E, dalloc(&s.lb_agg, ntiles), "hipMalloc look-back");
+        HIPTRY(E, dalloc(&s.lb_inc, ntiles), "hipMalloc look-back");
+        HIPTRY(E, hipMemsetAsync(s.lb_flag, 0, ntiles * 4, E.stream), "clear look-back");
         s.lb_cap = ntiles;
     }
     const uint64_t tcap = bytes + 64;
     if (tcap > s.text_cap)
-        ICHK(igrow(&s.text, s.text_cap, std::max<uint64_t>(tcap, 2 * s.text_cap)), "hipMalloc text");
+        HIPTRY(E, igrow(&s.text, s.text_cap, std::max<uint64_t>(tcap, 2 * s.text_cap)), "hipMalloc text");
     if (!s.hanc) {  // (stamps of call 0: no call reads them)
-        ICHK(dalloc(&s.hanc, (uint64_t)kIncMax), "hipMalloc search anchors");
-        ICHK(hipMemset(s.hanc, 0, kIncMax * 8ull), "clear search anchors");
+        HIPTRY(E, dalloc(&s.hanc, (uint64_t)kIncMax), "hipMalloc search anchors");
+        HIPTRY(E, hipMemset(s.hanc, 0, kIncMax * 8ull), "clear search anchors");
     }
     if (!s.ctl) {
-        ICHK(dalloc(&s.ctl, (uint64_t)I_N), "hipMalloc counters");
-        ICHK(hipMemset(s.ctl, 0, I_N * 8), "clear counters");
+        HIPTRY(E, dalloc(&s.ctl, (uint64_t)I_N), "hipMalloc counters");
+        HIPTRY(E, hipMemset(s.ctl, 0, I_N * 8), "clear counters");
     }
     if (!s.hres) {
-        ICHK(hipHostMalloc(reinterpret_cast<void**>(&s.hres), 64,
-                           hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc result");
+        HIPTRY(E, hipHostMalloc(reinterpret_cast<void**>(&s.hres), 64,
+                                hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc result");
         std::memset(s.hres, 0, 64);
-        ICHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.dres), s.hres, 0),
-             "mapped result pointer");
+        HIPTRY(E, hipHostGetDevicePointer(reinterpret_cast<void**>(&s.dres), s.hres, 0),
+                  "mapped result pointer");
     }
     return CRDT_HIP_OK;
 }
@@ -1015,7 +1005,7 @@ int inc_hasl(Engine& E, Replica& r, IncState& s, uint32_t lo, uint32_t hi) {
     if (!r.logs.fugue || hi < lo) return CRDT_HIP_OK;
     k_inc_hasl<<<std::max<uint32_t>(1, std::min<uint32_t>(grid_for(hi - lo + 1u, 256), 1024)), 256, 0,
                  E.stream>>>(r.logs.parent, r.logs.cp, lo, hi, s.hasl);
-    ICHK(hipGetLastError(), "left-child bits");
+    HIPTRY(E, hipGetLastError(), "left-child bits");
     return CRDT_HIP_OK;
 }
 
@@ -1032,22 +1022,22 @@ bool inc_profile() {
 // One launch, then a wait for the result block (sync: for the whole stream).
 int inc_run(Engine& E, IncState& s, IncArgs& a, bool sync) {
     hipStream_t st = E.stream;
-    ICHK(inc_setup(), "incremental merge setup");
+    HIPTRY(E, inc_setup(), "incremental merge setup");
     const bool prof = inc_profile();
     hipEvent_t* ev = s.pev;  // (per state: a state lives on one context and device)
     if (prof && !ev[0]) {
-        for (int k = 0; k < 2; ++k) ICHK(hipEventCreate(&ev[k]), "event");
-        ICHK(dalloc(&s.tsp, 16), "timestamps");
+        for (int k = 0; k < 2; ++k) HIPTRY(E, hipEventCreate(&ev[k]), "event");
+        HIPTRY(E, dalloc(&s.tsp, 16), "timestamps");
     }
     uint64_t* tsp = s.tsp;
     a.tsp = prof ? tsp : nullptr;
     const auto h0 = std::chrono::steady_clock::now();
-    if (prof) ICHK(hipEventRecord(ev[0], st), "event");
+    if (prof) HIPTRY(E, hipEventRecord(ev[0], st), "event");
     // (RGA: leading search workgroups for the roots an old sibling may precede)
     a.nsearch = a.m && !a.hasl ? std::min(a.m, kIncSearchers) : 0u;
     k_inc<<<a.nsearch + a.nblk, kIncThreads, inc_forest_lds(kIncMax), st>>>(a);
-    ICHK(hipGetLastError(), "incremental merge launch");
-    if (prof) ICHK(hipEventRecord(ev[1], st), "event");
+    HIPTRY(E, hipGetLastError(), "incremental merge launch");
+    if (prof) HIPTRY(E, hipEventRecord(ev[1], st), "event");
     const auto h1 = std::chrono::steady_clock::now();
     // The result block is written last, after a system-scope fence, so the host can take it as
     // soon as it lands instead of waiting for the stream to report completion (a blocking wait
@@ -1070,13 +1060,13 @@ int inc_run(Engine& E, IncState& s, IncArgs& a, bool sync) {
         }
         std::atomic_thread_fence(std::memory_order_acquire);
     }
-    if (!landed) ICHK(hipStreamSynchronize(st), "incremental merge sync");
+    if (!landed) HIPTRY(E, hipStreamSynchronize(st), "incremental merge sync");
     if (prof) {
         const auto h2 = std::chrono::steady_clock::now();
         float t = 0;
         (void)hipEventElapsedTime(&t, ev[0], ev[1]);
         uint64_t ts[11] = {};
-        if (a.m) ICHK(hipMemcpy(ts, tsp, sizeof(ts), hipMemcpyDeviceToHost), "timestamps");
+        if (a.m) HIPTRY(E, hipMemcpy(ts, tsp, sizeof(ts), hipMemcpyDeviceToHost), "timestamps");
         std::fprintf(stderr, "[inc] m %u n0 %u tiles %u | kernel %.1f us | forest", a.m, a.n0,
                      a.nblk, 1e3 * t);
         for (int k = 1; k < 11; ++k) std::fprintf(stderr, " %.1f", (ts[k] - ts[k - 1]) / 100.0);
@@ -1112,15 +1102,15 @@ int inc_rebuild(Engine& E, Replica& r, IncState& s) {
     s.hseq.resize((size_t)r.n + 1);
     s.hseq[0] = 0;
     if (r.n) std::memcpy(s.hseq.data() + 1, raw.data(), raw.size());
-    ICHK(hipMemcpyAsync(s.seq[s.cur], s.hseq.data(), (r.n + 1ull) * 4, hipMemcpyHostToDevice, st),
-         "upload order");
+    HIPTRY(E, hipMemcpyAsync(s.seq[s.cur], s.hseq.data(), (r.n + 1ull) * 4, hipMemcpyHostToDevice, st),
+              "upload order");
     // the largest key, into the slot the next call reads (that call copies it forward)
-    ICHK(hipMemsetAsync(s.ctl, 0, I_N * 8, st), "clear counters");
+    HIPTRY(E, hipMemsetAsync(s.ctl, 0, I_N * 8, st), "clear counters");
     const uint64_t next = s.calls + 1;
     k_inc_maxkey<<<std::max<uint32_t>(1, std::min<uint32_t>(grid_for(r.n, 256), 1024)), 256, 0, st>>>(
         r.logs.key, r.n, s.ctl + I_MAXKEY + ((next & 1u) ^ 1u));
     if (r.logs.fugue) {  // the left-child bits of the whole log
-        ICHK(hipMemsetAsync(s.hasl, 0, (s.cap / 32 + 1) * 4, st), "clear left-child bits");
+        HIPTRY(E, hipMemsetAsync(s.hasl, 0, (s.cap / 32 + 1) * 4, st), "clear left-child bits");
         if ((rc = inc_hasl(E, r, s, 1u, r.n))) return rc;
     }
     IncArgs a = make_args(r, s, r.n, 0);  // m = 0: the splice copies the order and sets the ranks
@@ -1162,7 +1152,7 @@ int replica_merge_inc(Engine& E, Replica& r, std::vector<uint8_t>* text, uint64_
     if (rc) return rc;
     IncState& s = r.inc;
     if (path) *path = 0;
-    ICHK(hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     // (the look-back packs {bytes, codepoints} as two u32 halves: a text of 4 GiB or more merges
     // in full)
     bool fast = s.valid && r.n >= s.n && r.n - s.n <= kIncMax && r.vis_bytes < (1ull << 32);
@@ -1199,8 +1189,22 @@ int replica_merge_inc(Engine& E, Replica& r, std::vector<uint8_t>* text, uint64_
     if (text) {
         text->resize(s.hres[1]);
         if (!text->empty())
-            ICHK(hipMemcpy(text->data(), s.text, text->size(), hipMemcpyDeviceToHost), "copy text");
+            HIPTRY(E, hipMemcpy(text->data(), s.text, text->size(), hipMemcpyDeviceToHost), "copy text");
     }
+    return CRDT_HIP_OK;
+}
+
+int replica_kept_order(Engine& E, Replica& r, const char* who, const uint32_t** seq,
+                       uint32_t* ntiles) {
+    const int rc = replica_merge_inc(E, r, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    const IncState& s = r.inc;
+    if (!s.valid || s.n != r.n || s.cap < (uint64_t)r.n + 1 || (uint64_t)r.n + 1 > r.logs.cap_slots) {
+        E.err = std::string(who) + ": the kept document order does not cover the replica";
+        return CRDT_HIP_EBADLOG;
+    }
+    *seq = s.seq[s.cur];
+    *ntiles = (uint32_t)(((uint64_t)r.n + 1 + kOrderTile - 1) / kOrderTile);  // ranks 0..n
     return CRDT_HIP_OK;
 }
 

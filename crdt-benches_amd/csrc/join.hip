@@ -157,16 +157,7 @@ __global__ __launch_bounds__(kJB) void k_join_probe(JoinArgs a) {
         mn = k;
         bool full = false;
         if (tab_insert<FUGUE>(a.stab, a.smask, a.skey, (uint32_t)s, k, full) != kEmpty) err |= EJ_DUP_SRC;
-        uint32_t d = kEmpty, h = jhash(k) & a.dmask;
-        for (uint32_t it = 0; it <= a.dmask; ++it) {
-            const uint32_t e = a.dtab[h];
-            if (e == kEmpty) break;
-            if (jident<FUGUE>(a.dkey[e]) == k) {
-                d = e;
-                break;
-            }
-            h = (h + 1u) & a.dmask;
-        }
+        const uint32_t d = tab_find<FUGUE>(a.dtab, a.dmask, a.dkey, k);
         if (full) err |= EJ_TABLE;
         a.map[s - a.P] = d;
         isnew = d == kEmpty ? 1u : 0u;
@@ -181,26 +172,14 @@ __global__ __launch_bounds__(kJB) void k_join_probe(JoinArgs a) {
 // One workgroup: block counts -> exclusive prefixes, the total.
 __global__ __launch_bounds__(1024) void k_join_top(JoinArgs a) {
     __shared__ uint32_t l0[16];
-    uint32_t c0 = 0;
-    for (uint32_t base = 0; base < a.nblk; base += 1024) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < a.nblk ? a.blk[i] : 0u;
-        uint32_t t0;
-        const uint32_t e0 = block_excl_scan<16>(v, l0, t0);
-        if (i < a.nblk) a.blk[i] = c0 + e0;
-        c0 += t0;
-    }
+    const uint32_t c0 = (uint32_t)block_scan_counts<1024>(a.blk, a.nblk, l0);
     if (threadIdx.x == 0) a.ctl[J_ADDED] = c0;
 }
 
 // New items take their dst ids, in src's slot order.
 __global__ __launch_bounds__(kJB) void k_join_rank(JoinArgs a) {
-    __shared__ uint32_t lds[kJB / 64];
     const uint64_t s = (uint64_t)a.P + (uint64_t)blockIdx.x * kJB + threadIdx.x;
-    const bool isnew = s <= a.ns && a.map[s - a.P] == kEmpty;
-    uint32_t tot;
-    const uint32_t e = block_excl_scan<kJB / 64>(isnew ? 1u : 0u, lds, tot);
-    if (isnew) a.map[s - a.P] = a.nd + 1u + a.blk[blockIdx.x] + e;
+    rank_new(a.map, a.blk, a.nd + 1u, s - a.P, s <= a.ns);
 }
 
 // The dst id of src's slot p (map is complete: k_join_rank ran before).
@@ -280,61 +259,10 @@ __global__ __launch_bounds__(kJB) void k_join_apply(JoinArgs a) {
     }
 }
 
-int jfail(Engine& E, const char* what, hipError_t e) {
-    E.err = std::string(what) + ": " + hipGetErrorString(e);
-    (void)hipGetLastError();
-    return CRDT_HIP_EDEVICE;
-}
-
-#define JCHK(expr, what)                                 \
-    do {                                                 \
-        hipError_t _e = (expr);                          \
-        if (_e != hipSuccess) return jfail(E, what, _e); \
-    } while (0)
-
-// A join's transient device arrays and counters, released after a wait for the stream.
-struct JoinScratch {
-    hipStream_t stream = nullptr;
-    uint32_t* dtab = nullptr;
-    uint32_t* stab = nullptr;
-    uint32_t* map = nullptr;
-    uint32_t* blk = nullptr;
-    uint64_t* ctl = nullptr;
-    uint64_t* hctl = nullptr;  // pinned host copy
-    hipEvent_t ev[2] = {nullptr, nullptr};  // around each group of kernels
-    uint64_t dev_ns = 0;                    // their summed device time
-    hipError_t time_begin() {
-        for (hipEvent_t& e : ev)
-            if (!e) {
-                const hipError_t rc = hipEventCreate(&e);
-                if (rc != hipSuccess) return rc;
-            }
-        return hipEventRecord(ev[0], stream);
-    }
-    hipError_t time_end() { return hipEventRecord(ev[1], stream); }
-    void time_add() {  // (after a wait for the stream)
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) dev_ns += (uint64_t)(ms * 1e6);
-    }
-    void drop_tables() {
-        for (void* p : {(void*)dtab, (void*)stab, (void*)map, (void*)blk})
-            if (p) pool_free(p, false, true);
-        dtab = stab = map = blk = nullptr;
-    }
-    ~JoinScratch() {
-        (void)hipStreamSynchronize(stream);
-        drop_tables();
-        if (ctl) pool_free(ctl, false, true);
-        if (hctl) pool_free(hctl, true);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
 // Everything after the prefix pass, with slots 1..P-1 taken as the common prefix.  Leaves the
 // final counters in sc.hctl (after a wait).
 template <bool FUGUE>
-int join_run(Engine& E, Replica& dst, const Replica& src, JoinScratch& sc, uint32_t P) {
+int join_run(Engine& E, Replica& dst, const Replica& src, CallScratch& sc, uint32_t P) {
     const uint32_t nd = dst.n, ns = src.n;
     hipStream_t s = E.stream;
     // appended items: at most src's slots past the prefix
@@ -343,14 +271,14 @@ int join_run(Engine& E, Replica& dst, const Replica& src, JoinScratch& sc, uint3
     const uint64_t cd = nd >= P ? nd - P + 1ull : 0, cs = ns >= P ? ns - P + 1ull : 0;
     const uint64_t dcap = pow2_at_least(2 * cd), scap = pow2_at_least(2 * cs);
     const uint32_t nblk = grid_for(cs, kJB);
-    sc.drop_tables();  // (a second run: the first one's arrays; the stream is idle)
-    JCHK(dalloc(&sc.dtab, dcap), "hipMalloc join table");
-    JCHK(dalloc(&sc.stab, scap), "hipMalloc join table");
-    JCHK(dalloc(&sc.map, cs), "hipMalloc join map");
-    JCHK(dalloc(&sc.blk, (uint64_t)nblk), "hipMalloc join blocks");
-    JCHK(hipMemsetAsync(sc.dtab, 0xFF, dcap * 4, s), "memset join table");
-    JCHK(hipMemsetAsync(sc.stab, 0xFF, scap * 4, s), "memset join table");
+    sc.drop_arrays();  // (a second run: the first one's arrays; the stream is idle)
     JoinArgs a{};
+    HIPTRY(E, sc.alloc(&a.dtab, dcap), "hipMalloc join table");
+    HIPTRY(E, sc.alloc(&a.stab, scap), "hipMalloc join table");
+    HIPTRY(E, sc.alloc(&a.map, cs), "hipMalloc join map");
+    HIPTRY(E, sc.alloc(&a.blk, (uint64_t)nblk), "hipMalloc join blocks");
+    HIPTRY(E, hipMemsetAsync(a.dtab, 0xFF, dcap * 4, s), "memset join table");
+    HIPTRY(E, hipMemsetAsync(a.stab, 0xFF, scap * 4, s), "memset join table");
     a.dpar = dst.logs.parent;
     a.dkey = dst.logs.key;
     a.dcp = dst.logs.cp;
@@ -363,15 +291,11 @@ int join_run(Engine& E, Replica& dst, const Replica& src, JoinScratch& sc, uint3
     a.ns = ns;
     a.P = P;
     a.cap_slots = dst.logs.cap_slots;
-    a.dtab = sc.dtab;
     a.dmask = (uint32_t)(dcap - 1);
-    a.stab = sc.stab;
     a.smask = (uint32_t)(scap - 1);
-    a.map = sc.map;
-    a.blk = sc.blk;
     a.nblk = nblk;
     a.ctl = sc.ctl;
-    JCHK(sc.time_begin(), "join event");
+    HIPTRY(E, sc.time_begin(), "join event");
     k_join_init<<<1, 64, 0, s>>>(sc.ctl, 0);
     if (P > 1) k_join_pmax<FUGUE><<<grid_stride(P - 1), kJB, 0, s>>>(a);
     if (cd) k_join_table<FUGUE><<<grid_stride(cd), kJB, 0, s>>>(a);
@@ -382,10 +306,10 @@ int join_run(Engine& E, Replica& dst, const Replica& src, JoinScratch& sc, uint3
         k_join_apply<false, FUGUE><<<grid_stride(cs), kJB, 0, s>>>(a);
     }
     k_join_apply<true, FUGUE><<<grid_stride(ns), kJB, 0, s>>>(a);
-    JCHK(hipGetLastError(), "join kernels");
-    JCHK(sc.time_end(), "join event");
-    JCHK(hipMemcpyAsync(sc.hctl, sc.ctl, J_N * 8, hipMemcpyDeviceToHost, s), "copy join counters");
-    JCHK(hipStreamSynchronize(s), "join sync");
+    HIPTRY(E, hipGetLastError(), "join kernels");
+    HIPTRY(E, sc.time_end(), "join event");
+    HIPTRY(E, hipMemcpyAsync(sc.hctl, sc.ctl, J_N * 8, hipMemcpyDeviceToHost, s), "copy join counters");
+    HIPTRY(E, hipStreamSynchronize(s), "join sync");
     sc.time_add();
     return CRDT_HIP_OK;
 }
@@ -407,16 +331,14 @@ int replica_join(Engine& E, Replica& dst, const Replica& src, uint32_t* added,
         E.err = "replica has an unsettled decode";
         return CRDT_HIP_EINVAL;
     }
-    JCHK(hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     int rc = replica_settle(E, dst);
     if (rc) return rc;
     const uint32_t nd = dst.n, ns = src.n;
     if (ns == 0) return CRDT_HIP_OK;  // nothing to take
     hipStream_t s = E.stream;
-    JoinScratch sc;
-    sc.stream = s;
-    JCHK(dalloc(&sc.ctl, (uint64_t)J_N), "hipMalloc join counters");
-    JCHK(pool_alloc(reinterpret_cast<void**>(&sc.hctl), J_N * 8, true), "hipHostMalloc");
+    CallScratch sc(s);
+    HIPTRY(E, sc.counters(J_N), "hipMalloc join counters");
 
     // ---- the common prefix ---------------------------------------------------------------------
     const uint32_t m = std::min(nd, ns);
@@ -430,13 +352,13 @@ int replica_join(Engine& E, Replica& dst, const Replica& src, uint32_t* added,
         a.skey = src.logs.key;
         a.scp = src.logs.cp;
         a.ctl = sc.ctl;
-        JCHK(sc.time_begin(), "join event");
+        HIPTRY(E, sc.time_begin(), "join event");
         k_join_init<<<1, 64, 0, s>>>(sc.ctl, m);
         k_join_prefix<<<grid_stride(m), kJB, 0, s>>>(a, m);
-        JCHK(hipGetLastError(), "join prefix kernel");
-        JCHK(sc.time_end(), "join event");
-        JCHK(hipMemcpyAsync(sc.hctl, sc.ctl, J_N * 8, hipMemcpyDeviceToHost, s), "copy join counters");
-        JCHK(hipStreamSynchronize(s), "join sync");
+        HIPTRY(E, hipGetLastError(), "join prefix kernel");
+        HIPTRY(E, sc.time_end(), "join event");
+        HIPTRY(E, hipMemcpyAsync(sc.hctl, sc.ctl, J_N * 8, hipMemcpyDeviceToHost, s), "copy join counters");
+        HIPTRY(E, hipStreamSynchronize(s), "join sync");
         sc.time_add();
         P = (uint32_t)sc.hctl[J_FIRST];
         if (sc.hctl[J_BADCP] < P) {

@@ -11,7 +11,7 @@
 //
 //   k_mark_pack      one pass over the 3-byte codepoint column: the wave ballots the tombstone
 //                    flags and one lane stores each 64-bit word of the mark's bit plane
-//   k_patch_classify a workgroup per tile of kPatchTile = 4,096 consecutive ranks, four ranks per
+//   k_patch_classify a workgroup per tile of kOrderTile = 4,096 consecutive ranks, four ranks per
 //                    thread (one 16-byte load of the order); per rank the slot's codepoint word
 //                    and its mark bit are gathered (typing runs make both mostly coalesced) and
 //                    the item is K (was and now), D (was, not now), I (now, not was) or nothing.
@@ -47,18 +47,13 @@
 
 #include "idtab.hpp"
 #include "oplog.hpp"
+#include "order.hpp"
 #include "replica.hpp"
 #include "util.hpp"
 #include "wave.hpp"
 
 namespace crdt {
 namespace {
-
-constexpr uint32_t kPT = 1024;                 // threads of a tile's workgroup
-constexpr uint32_t kPerThread = kPatchTile / kPT;  // consecutive ranks per thread
-static_assert(kPerThread == 4, "a thread loads its ranks as one uint4");
-constexpr uint32_t kPW = kPT / 64;             // waves per workgroup
-constexpr int kTop = 256;                      // threads of k_patch_top (a tile aggregate each)
 
 // classes of an item (0: neither was nor now; also "no item" as a carried class)
 constexpr uint32_t C_NONE = 0, C_K = 1, C_D = 2, C_I = 3;
@@ -115,36 +110,20 @@ __global__ __launch_bounds__(kJB) void k_mark_pack(const uint8_t* cp, uint32_t n
 // ---- classify ----------------------------------------------------------------------------------
 // The classes and codepoints of the thread's four ranks k0..k0 + 3 (ranks past n, rank 0 and
 // slots that are no item: C_NONE).
-__device__ __forceinline__ void patch_load(const PatchArgs& a, uint64_t k0, uint32_t cls[kPerThread],
-                                           uint32_t cpw[kPerThread], uint64_t& err) {
-    uint32_t sl[kPerThread];
-    if (k0 + kPerThread - 1 <= a.n) {
-        const uint4 v = *reinterpret_cast<const uint4*>(a.seq + k0);  // (k0 is a multiple of 4)
-        sl[0] = v.x;
-        sl[1] = v.y;
-        sl[2] = v.z;
-        sl[3] = v.w;
-    } else {
+__device__ __forceinline__ void patch_load(const PatchArgs& a, uint64_t k0, uint32_t cls[kOrdPer],
+                                           uint32_t cpw[kOrdPer], uint64_t& err) {
 #pragma unroll
-        for (uint32_t j = 0; j < kPerThread; ++j) sl[j] = k0 + j <= a.n ? a.seq[k0 + j] : 0u;
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < kPerThread; ++j) {
-        const uint32_t s = sl[j];
+    for (uint32_t j = 0; j < kOrdPer; ++j) {
         cls[j] = C_NONE;
         cpw[j] = 0;
-        if (k0 + j == 0 || k0 + j > a.n) continue;
-        if (s == 0 || s > a.n) {
-            err |= EP_SLOT;
-            continue;
-        }
-        const uint32_t c = cp3_get(a.cp, s);
+    }
+    order_load4(a.seq, a.cp, a.n, k0, err, EP_SLOT, [&](uint32_t j, uint32_t s, uint32_t c) {
         const bool now = !(c & kDelBit);
         const bool was = s <= a.n_mark && (uint64_t)(s >> 6) < a.mark_words &&
                          !((a.mark[s >> 6] >> (s & 63u)) & 1ull);
         cls[j] = was ? (now ? C_K : C_D) : (now ? C_I : C_NONE);
         cpw[j] = c & 0x001FFFFFu;
-    }
+    });
 }
 
 // What a thread's four items add up to.  `heads` counts the D or I items whose previous K, D or I
@@ -153,11 +132,11 @@ __device__ __forceinline__ void patch_load(const PatchArgs& a, uint64_t k0, uint
 struct ThreadSum {
     uint32_t now, del, ibytes, heads, first, last;
 };
-__device__ __forceinline__ ThreadSum patch_sum(const uint32_t cls[kPerThread],
-                                               const uint32_t cpw[kPerThread]) {
+__device__ __forceinline__ ThreadSum patch_sum(const uint32_t cls[kOrdPer],
+                                               const uint32_t cpw[kOrdPer]) {
     ThreadSum t{0, 0, 0, 0, C_NONE, C_NONE};
 #pragma unroll
-    for (uint32_t j = 0; j < kPerThread; ++j) {
+    for (uint32_t j = 0; j < kOrdPer; ++j) {
         const uint32_t c = cls[j];
         if (c == C_NONE) continue;
         if (c != C_D) t.now++;
@@ -171,7 +150,7 @@ __device__ __forceinline__ ThreadSum patch_sum(const uint32_t cls[kPerThread],
 }
 
 // The class of the last K, D or I item of the tile before this thread's items (C_NONE: the tile
-// holds none before them).  wlast: kPW entries of LDS.  Called by every thread of the block.
+// holds none before them).  wlast: kOrdW entries of LDS.  Called by every thread of the block.
 __device__ __forceinline__ uint32_t patch_incoming(uint32_t last, uint32_t* wlast) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint64_t has = __ballot(last != C_NONE);
@@ -185,7 +164,7 @@ __device__ __forceinline__ uint32_t patch_incoming(uint32_t last, uint32_t* wlas
     __syncthreads();
     uint32_t carry = C_NONE;  // the last class of the nearest earlier wave that holds an item
 #pragma unroll
-    for (uint32_t i = 0; i < kPW; ++i) {
+    for (uint32_t i = 0; i < kOrdW; ++i) {
         const uint32_t x = wlast[i];
         if (i < w && x != C_NONE) carry = x;
     }
@@ -193,11 +172,11 @@ __device__ __forceinline__ uint32_t patch_incoming(uint32_t last, uint32_t* wlas
     return below ? inwave : carry;
 }
 
-__global__ __launch_bounds__(kPT) void k_patch_classify(PatchArgs a) {
-    __shared__ uint32_t red[kPW];
-    __shared__ uint32_t wfirst[kPW];
-    const uint64_t k0 = (uint64_t)blockIdx.x * kPatchTile + (uint64_t)threadIdx.x * kPerThread;
-    uint32_t cls[kPerThread], cpw[kPerThread];
+__global__ __launch_bounds__(kOrdT) void k_patch_classify(PatchArgs a) {
+    __shared__ uint32_t red[kOrdW];
+    __shared__ uint32_t wfirst[kOrdW];
+    const uint64_t k0 = (uint64_t)blockIdx.x * kOrderTile + (uint64_t)threadIdx.x * kOrdPer;
+    uint32_t cls[kOrdPer], cpw[kOrdPer];
     uint64_t err = 0;
     patch_load(a, k0, cls, cpw, err);
     ctl_or(&a.ctl[P_ERR], err);
@@ -214,21 +193,21 @@ __global__ __launch_bounds__(kPT) void k_patch_classify(PatchArgs a) {
     if ((threadIdx.x & 63u) == 0) wfirst[threadIdx.x >> 6] = has ? wf : C_NONE;
     __syncthreads();
     uint32_t first = C_NONE, last = C_NONE;
-    if (threadIdx.x == kPT - 1) {
-        for (uint32_t i = kPW; i-- > 0;)
+    if (threadIdx.x == kOrdT - 1) {
+        for (uint32_t i = kOrdW; i-- > 0;)
             if (wfirst[i] != C_NONE) first = wfirst[i];
         last = t.last != C_NONE ? t.last : inc;
     }
     __syncthreads();
-    const uint32_t s_now = block_sum_t0<kPW>(t.now, red), s_del = block_sum_t0<kPW>(t.del, red);
-    const uint32_t s_ib = block_sum_t0<kPW>(t.ibytes, red), s_h = block_sum_t0<kPW>(heads, red);
+    const uint32_t s_now = block_sum_t0<kOrdW>(t.now, red), s_del = block_sum_t0<kOrdW>(t.del, red);
+    const uint32_t s_ib = block_sum_t0<kOrdW>(t.ibytes, red), s_h = block_sum_t0<kOrdW>(heads, red);
     if (threadIdx.x == 0 && blockIdx.x < a.ntiles) {
         a.agg[blockIdx.x].now = s_now;
         a.agg[blockIdx.x].del = s_del;
         a.agg[blockIdx.x].ibytes = s_ib;
         a.agg[blockIdx.x].heads = s_h;
     }
-    if (threadIdx.x == kPT - 1 && blockIdx.x < a.ntiles) {
+    if (threadIdx.x == kOrdT - 1 && blockIdx.x < a.ntiles) {
         a.agg[blockIdx.x].first = first;
         a.agg[blockIdx.x].last = last;
     }
@@ -260,28 +239,28 @@ __device__ __forceinline__ uint32_t block_excl_max(uint32_t x, uint32_t* lds, ui
     return lane ? max(off, prev) : off;
 }
 
-__global__ __launch_bounds__(kTop) void k_patch_top(PatchArgs a) {
-    __shared__ uint32_t lds[kTop / 64];
+__global__ __launch_bounds__(kOrdTop) void k_patch_top(PatchArgs a) {
+    __shared__ uint32_t lds[kOrdTop / 64];
     uint64_t c_now = 0, c_del = 0, c_ib = 0, c_heads = 0;
     uint32_t c_last = 0;  // (tile index + 1) << 2 | class of the last tile so far that holds an item
-    for (uint32_t base = 0; base < a.ntiles; base += kTop) {
+    for (uint32_t base = 0; base < a.ntiles; base += kOrdTop) {
         const uint32_t i = base + threadIdx.x;
         TileAgg g{0, 0, 0, 0, C_NONE, C_NONE};
         if (i < a.ntiles) g = a.agg[i];
         uint32_t tot;
-        const uint32_t seen = max(c_last, block_excl_max<kTop / 64>(g.last != C_NONE ? ((i + 1u) << 2) | g.last : 0u, lds, tot));
+        const uint32_t seen = max(c_last, block_excl_max<kOrdTop / 64>(g.last != C_NONE ? ((i + 1u) << 2) | g.last : 0u, lds, tot));
         c_last = max(c_last, tot);
         const uint32_t carry = seen & 3u;  // (C_NONE: the start of the document)
         const uint32_t heads = g.heads + (g.first >= C_D && (carry == C_K || carry == C_NONE) ? 1u : 0u);
         TilePre p;
         p.carry = carry;
-        p.now = (uint32_t)c_now + block_excl_scan<kTop / 64>(g.now, lds, tot);
+        p.now = (uint32_t)c_now + block_excl_scan<kOrdTop / 64>(g.now, lds, tot);
         c_now += tot;
-        p.del = (uint32_t)c_del + block_excl_scan<kTop / 64>(g.del, lds, tot);
+        p.del = (uint32_t)c_del + block_excl_scan<kOrdTop / 64>(g.del, lds, tot);
         c_del += tot;
-        p.ibytes = c_ib + block_excl_scan<kTop / 64>(g.ibytes, lds, tot);
+        p.ibytes = c_ib + block_excl_scan<kOrdTop / 64>(g.ibytes, lds, tot);
         c_ib += tot;
-        p.heads = (uint32_t)c_heads + block_excl_scan<kTop / 64>(heads, lds, tot);
+        p.heads = (uint32_t)c_heads + block_excl_scan<kOrdTop / 64>(heads, lds, tot);
         c_heads += tot;
         if (i < a.ntiles) a.pre[i] = p;
     }
@@ -294,11 +273,11 @@ __global__ __launch_bounds__(kTop) void k_patch_top(PatchArgs a) {
 }
 
 // ---- write -------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kPT) void k_patch_write(PatchArgs a) {
-    __shared__ uint32_t lds[kPW];
+__global__ __launch_bounds__(kOrdT) void k_patch_write(PatchArgs a) {
+    __shared__ uint32_t lds[kOrdW];
     if (blockIdx.x >= a.ntiles) return;
-    const uint64_t k0 = (uint64_t)blockIdx.x * kPatchTile + (uint64_t)threadIdx.x * kPerThread;
-    uint32_t cls[kPerThread], cpw[kPerThread];
+    const uint64_t k0 = (uint64_t)blockIdx.x * kOrderTile + (uint64_t)threadIdx.x * kOrdPer;
+    uint32_t cls[kOrdPer], cpw[kOrdPer];
     uint64_t err = 0;
     patch_load(a, k0, cls, cpw, err);  // (k_patch_classify reported any error)
     const ThreadSum t = patch_sum(cls, cpw);
@@ -309,13 +288,13 @@ __global__ __launch_bounds__(kPT) void k_patch_write(PatchArgs a) {
     if (inc == C_NONE) inc = p.carry == C_NONE ? C_K : p.carry;
     const uint32_t heads = t.heads + (t.first >= C_D && inc == C_K ? 1u : 0u);
     uint32_t tot;
-    uint64_t now = (uint64_t)p.now + block_excl_scan<kPW>(t.now, lds, tot);
-    uint32_t del = p.del + block_excl_scan<kPW>(t.del, lds, tot);
-    uint64_t ib = p.ibytes + block_excl_scan<kPW>(t.ibytes, lds, tot);
-    uint32_t h = p.heads + block_excl_scan<kPW>(heads, lds, tot);
+    uint64_t now = (uint64_t)p.now + block_excl_scan<kOrdW>(t.now, lds, tot);
+    uint32_t del = p.del + block_excl_scan<kOrdW>(t.del, lds, tot);
+    uint64_t ib = p.ibytes + block_excl_scan<kOrdW>(t.ibytes, lds, tot);
+    uint32_t h = p.heads + block_excl_scan<kOrdW>(heads, lds, tot);
     uint32_t prev = inc;
 #pragma unroll
-    for (uint32_t j = 0; j < kPerThread; ++j) {
+    for (uint32_t j = 0; j < kOrdPer; ++j) {
         const uint32_t c = cls[j];
         if (c == C_NONE) continue;
         if (c != C_K && prev == C_K) {
@@ -368,62 +347,15 @@ __global__ __launch_bounds__(kJB) void k_patch_finish(PatchArgs a, uint32_t tota
     a.out[h] = r;
 }
 
-// ---- host side ---------------------------------------------------------------------------------
-int pfail(Engine& E, const char* what, hipError_t e) {
-    E.err = std::string(what) + ": " + hipGetErrorString(e);
-    (void)hipGetLastError();
-    return CRDT_HIP_EDEVICE;
-}
-#define PCHK(expr, what)                                 \
-    do {                                                 \
-        hipError_t _e = (expr);                          \
-        if (_e != hipSuccess) return pfail(E, what, _e); \
-    } while (0)
-
-// A call's transient device arrays, counters and events, released after a wait for the stream.
-struct PatchScratch {
-    hipStream_t stream = nullptr;
-    std::vector<void*> dev;
-    uint64_t* ctl = nullptr;
-    uint64_t* hctl = nullptr;  // pinned host copy
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    uint64_t dev_ns = 0;
-    template <class T>
-    hipError_t alloc(T** p, uint64_t count) {
-        const hipError_t rc = dalloc(p, count);
-        if (rc == hipSuccess) dev.push_back(*p);
-        return rc;
-    }
-    hipError_t time_begin() {
-        for (hipEvent_t& e : ev)
-            if (!e) {
-                const hipError_t rc = hipEventCreate(&e);
-                if (rc != hipSuccess) return rc;
-            }
-        return hipEventRecord(ev[0], stream);
-    }
-    hipError_t time_end() { return hipEventRecord(ev[1], stream); }
-    void time_add() {  // (after a wait for the stream)
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) dev_ns += (uint64_t)(ms * 1e6);
-    }
-    ~PatchScratch() {
-        (void)hipStreamSynchronize(stream);
-        for (void* p : dev) pool_free(p, false, true);
-        if (hctl) pool_free(hctl, true);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
 }  // namespace
 
+// ---- host side ---------------------------------------------------------------------------------
 DeviceMark::~DeviceMark() {
     if (bits) pool_free(bits);
 }
 
 int replica_mark(Engine& E, Replica& r, DeviceMark& m) {
-    PCHK(hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     int rc = replica_settle(E, r);
     if (rc) return rc;
     const uint64_t words = ((uint64_t)r.n + 1 + 63) / 64;
@@ -436,17 +368,17 @@ int replica_mark(Engine& E, Replica& r, DeviceMark& m) {
         pool_free(m.bits);
         m.bits = nullptr;
     }
-    PCHK(dalloc(&m.bits, words), "hipMalloc mark");
+    HIPTRY(E, dalloc(&m.bits, words), "hipMalloc mark");
     m.n = r.n;
     m.words = words;
     if (r.n == 0) {  // (an empty replica may have no columns yet)
         const uint64_t all = ~0ull;
-        PCHK(hipMemcpy(m.bits, &all, 8, hipMemcpyHostToDevice), "mark");
+        HIPTRY(E, hipMemcpy(m.bits, &all, 8, hipMemcpyHostToDevice), "mark");
         return CRDT_HIP_OK;
     }
     k_mark_pack<<<grid_for(words * 64, kJB), kJB, 0, E.stream>>>(r.logs.cp, r.n, m.bits, words);
-    PCHK(hipGetLastError(), "mark kernel");
-    PCHK(hipStreamSynchronize(E.stream), "mark sync");
+    HIPTRY(E, hipGetLastError(), "mark kernel");
+    HIPTRY(E, hipStreamSynchronize(E.stream), "mark sync");
     return CRDT_HIP_OK;
 }
 
@@ -456,7 +388,7 @@ int replica_patches_since(Engine& E, Replica& r, const DeviceMark& m, PatchRec* 
     if (stats) *stats = PatchStats{};
     *out_n = 0;
     *out_ins = 0;
-    PCHK(hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     int rc = replica_settle(E, r);
     if (rc) return rc;
     if (r.n < m.n || !m.bits || m.words != ((uint64_t)m.n + 1 + 63) / 64) {
@@ -464,38 +396,28 @@ int replica_patches_since(Engine& E, Replica& r, const DeviceMark& m, PatchRec* 
         return CRDT_HIP_EINVAL;
     }
     if (r.n == 0) return CRDT_HIP_OK;  // nothing held: nothing changed
-    // the document order of every item held, as a merge_inc leaves it
-    rc = replica_merge_inc(E, r, nullptr, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    const IncState& inc = r.inc;
-    if (!inc.valid || inc.n != r.n || inc.cap < (uint64_t)r.n + 1 || (uint64_t)r.n + 1 > r.logs.cap_slots) {
-        E.err = "patches: the kept document order does not cover the replica";
-        return CRDT_HIP_EBADLOG;
-    }
-    hipStream_t s = E.stream;
-    PatchScratch sc;
-    sc.stream = s;
     PatchArgs a{};
-    a.seq = inc.seq[inc.cur];
+    rc = replica_kept_order(E, r, "patches", &a.seq, &a.ntiles);
+    if (rc) return rc;
+    hipStream_t s = E.stream;
+    CallScratch sc(s);
     a.cp = r.logs.cp;
     a.mark = m.bits;
     a.n = r.n;
     a.n_mark = m.n;
     a.mark_words = m.words;
-    a.ntiles = (uint32_t)(((uint64_t)r.n + 1 + kPatchTile - 1) / kPatchTile);  // ranks 0..n
-    PCHK(sc.alloc(&sc.ctl, (uint64_t)P_N), "hipMalloc patch counters");
-    PCHK(pool_alloc(reinterpret_cast<void**>(&sc.hctl), P_N * 8, true), "hipHostMalloc patch counters");
-    PCHK(sc.alloc(&a.agg, (uint64_t)a.ntiles), "hipMalloc patch tiles");
-    PCHK(sc.alloc(&a.pre, (uint64_t)a.ntiles), "hipMalloc patch tiles");
+    HIPTRY(E, sc.counters(P_N), "hipMalloc patch counters");
+    HIPTRY(E, sc.alloc(&a.agg, (uint64_t)a.ntiles), "hipMalloc patch tiles");
+    HIPTRY(E, sc.alloc(&a.pre, (uint64_t)a.ntiles), "hipMalloc patch tiles");
     a.ctl = sc.ctl;
-    PCHK(sc.time_begin(), "patch event");
+    HIPTRY(E, sc.time_begin(), "patch event");
     k_patch_init<<<1, 64, 0, s>>>(sc.ctl);
-    k_patch_classify<<<a.ntiles, kPT, 0, s>>>(a);
-    k_patch_top<<<1, kTop, 0, s>>>(a);
-    PCHK(hipGetLastError(), "patch classify kernels");
-    PCHK(sc.time_end(), "patch event");
-    PCHK(hipMemcpyAsync(sc.hctl, sc.ctl, P_N * 8, hipMemcpyDeviceToHost, s), "copy patch counters");
-    PCHK(hipStreamSynchronize(s), "patch sync");  // the one wait: the sizes
+    k_patch_classify<<<a.ntiles, kOrdT, 0, s>>>(a);
+    k_patch_top<<<1, kOrdTop, 0, s>>>(a);
+    HIPTRY(E, hipGetLastError(), "patch classify kernels");
+    HIPTRY(E, sc.time_end(), "patch event");
+    HIPTRY(E, hipMemcpyAsync(sc.hctl, sc.ctl, P_N * 8, hipMemcpyDeviceToHost, s), "copy patch counters");
+    HIPTRY(E, hipStreamSynchronize(s), "patch sync");  // the one wait: the sizes
     sc.time_add();
     if (sc.hctl[P_ERR]) {
         E.err = "patches: the kept document order names a slot that is no item";
@@ -525,19 +447,19 @@ int replica_patches_since(Engine& E, Replica& r, const DeviceMark& m, PatchRec* 
     if (np == 0) return CRDT_HIP_OK;
     a.npatch = (uint32_t)np;
     a.nibytes = nib;
-    PCHK(sc.alloc(&a.hpos, np), "hipMalloc patch heads");
-    PCHK(sc.alloc(&a.hdel, np), "hipMalloc patch heads");
-    PCHK(sc.alloc(&a.hib, np), "hipMalloc patch heads");
-    PCHK(sc.alloc(&a.out, np), "hipMalloc patches");
-    PCHK(sc.alloc(&a.ins, nib), "hipMalloc patch text");
-    PCHK(sc.time_begin(), "patch event");
-    k_patch_write<<<a.ntiles, kPT, 0, s>>>(a);
+    HIPTRY(E, sc.alloc(&a.hpos, np), "hipMalloc patch heads");
+    HIPTRY(E, sc.alloc(&a.hdel, np), "hipMalloc patch heads");
+    HIPTRY(E, sc.alloc(&a.hib, np), "hipMalloc patch heads");
+    HIPTRY(E, sc.alloc(&a.out, np), "hipMalloc patches");
+    HIPTRY(E, sc.alloc(&a.ins, nib), "hipMalloc patch text");
+    HIPTRY(E, sc.time_begin(), "patch event");
+    k_patch_write<<<a.ntiles, kOrdT, 0, s>>>(a);
     k_patch_finish<<<grid_for(np, kJB), kJB, 0, s>>>(a, (uint32_t)sc.hctl[P_DEL]);
-    PCHK(hipGetLastError(), "patch write kernels");
-    PCHK(sc.time_end(), "patch event");
-    PCHK(hipMemcpyAsync(out, a.out, np * sizeof(PatchRec), hipMemcpyDeviceToHost, s), "copy patches");
-    if (nib) PCHK(hipMemcpyAsync(ins, a.ins, nib, hipMemcpyDeviceToHost, s), "copy patch text");
-    PCHK(hipStreamSynchronize(s), "patch sync");
+    HIPTRY(E, hipGetLastError(), "patch write kernels");
+    HIPTRY(E, sc.time_end(), "patch event");
+    HIPTRY(E, hipMemcpyAsync(out, a.out, np * sizeof(PatchRec), hipMemcpyDeviceToHost, s), "copy patches");
+    if (nib) HIPTRY(E, hipMemcpyAsync(ins, a.ins, nib, hipMemcpyDeviceToHost, s), "copy patch text");
+    HIPTRY(E, hipStreamSynchronize(s), "patch sync");
     sc.time_add();
     if (stats) stats->device_ns = sc.dev_ns;
     return CRDT_HIP_OK;

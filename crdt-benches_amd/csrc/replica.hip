@@ -340,18 +340,6 @@ __global__ void k_replay_check(uint64_t* ctl, uint32_t n0, uint64_t bytes0, uint
 
 thread_local uint64_t grow_gen = 0;  // counts grow() reallocations (replica generations)
 
-int hip_fail(Engine& E, const char* what, hipError_t e) {
-    E.err = std::string(what) + ": " + hipGetErrorString(e);
-    (void)hipGetLastError();
-    return CRDT_HIP_EDEVICE;
-}
-
-#define RCHK(expr, what)                                \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) return hip_fail(E, what, _e); \
-    } while (0)
-
 template <class T>
 hipError_t grow(T** p, uint64_t& cap, uint64_t need) {
     if (need <= cap) return hipSuccess;
@@ -408,7 +396,7 @@ int replica_reserve(Engine& E, Replica& r, uint64_t items) {
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(s);
         dfree(par); dfree(key); dfree(c);
-        return hip_fail(E, "replica reserve", e);
+        return E.fail("replica reserve", e);
     }
     // the old arrays may still be read by queued work: freed at the replica's next wait
     for (void* p : {(void*)L.parent, (void*)L.key, (void*)L.cp})
@@ -422,7 +410,7 @@ int replica_reserve(Engine& E, Replica& r, uint64_t items) {
 }
 
 int replica_upload(Engine& E, Replica& r, const crdt_hip_oplog_view* v) {
-    RCHK(hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     const uint32_t n = v ? v->n : 0u;
     int rc = replica_reserve(E, r, n);
     if (rc) return rc;
@@ -436,7 +424,7 @@ int replica_upload(Engine& E, Replica& r, const crdt_hip_oplog_view* v) {
     // on the engine stream, after the padding kernel replica_reserve may have queued there (a
     // null-stream copy does not wait for a non-blocking stream and could be overwritten by it)
     hipStream_t s = E.stream;
-    RCHK(hipMemcpyAsync(L.parent + 1, v->parent, n * 4ull, hipMemcpyHostToDevice, s), "upload parent");
+    HIPTRY(E, hipMemcpyAsync(L.parent + 1, v->parent, n * 4ull, hipMemcpyHostToDevice, s), "upload parent");
     std::vector<uint8_t> c(3ull * n);
     std::vector<uint64_t> key(n);
     for (uint32_t i = 0; i < n; ++i) {
@@ -453,14 +441,14 @@ int replica_upload(Engine& E, Replica& r, const crdt_hip_oplog_view* v) {
             r.vis_bytes += utf8_len_cp(v->cp[i] & kCpMaskR);
         }
     }
-    RCHK(hipMemcpyAsync(L.key + 1, key.data(), n * 8ull, hipMemcpyHostToDevice, s), "upload key");
-    RCHK(hipMemcpyAsync(L.cp + 3, c.data(), c.size(), hipMemcpyHostToDevice, s), "upload cp");
-    RCHK(hipStreamSynchronize(s), "upload sync");  // (key, c and the caller's view are released)
+    HIPTRY(E, hipMemcpyAsync(L.key + 1, key.data(), n * 8ull, hipMemcpyHostToDevice, s), "upload key");
+    HIPTRY(E, hipMemcpyAsync(L.cp + 3, c.data(), c.size(), hipMemcpyHostToDevice, s), "upload cp");
+    HIPTRY(E, hipStreamSynchronize(s), "upload sync");  // (key, c and the caller's view are released)
     return CRDT_HIP_OK;
 }
 
 int replica_copy(Engine& E, const Replica& src, Replica& dst) {
-    RCHK(hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     dst.inc.valid = false;
     if (src.pending) {
         E.err = "replica has an unsettled decode";
@@ -476,7 +464,7 @@ int replica_copy(Engine& E, const Replica& src, Replica& dst) {
         // (no wait: every later use of the copy, decode and merge, is on the same stream)
         k_rep_copy<<<(uint32_t)std::min<uint64_t>(grid_for(cap, kUB), 4096), kUB, 0, s>>>(
             S.parent, S.key, S.cp, D.parent, D.key, D.cp, cap);
-        RCHK(hipGetLastError(), "replica copy");
+        HIPTRY(E, hipGetLastError(), "replica copy");
     }
     dst.n = src.n;
     dst.agent = src.agent;
@@ -497,16 +485,16 @@ int updates_upload(Engine& E, UpdateBatch& ub, const uint8_t* buf, uint64_t len,
         E.err = "update batch of 4 GiB or more";
         return CRDT_HIP_ERANGE;
     }
-    RCHK(hipSetDevice(E.device), "hipSetDevice");
-    RCHK(dalloc(&ub.buf, (len + 4) & ~3ull), "hipMalloc update buffer");
-    RCHK(dalloc(&ub.off, n + 1ull), "hipMalloc update offsets");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, dalloc(&ub.buf, (len + 4) & ~3ull), "hipMalloc update buffer");
+    HIPTRY(E, dalloc(&ub.off, n + 1ull), "hipMalloc update offsets");
     // on the engine's stream (the decode kernels run there; a null-stream copy would not be
     // ordered with them), waited for before the caller's buffers may go
-    if (len) RCHK(hipMemcpyAsync(ub.buf, buf, len, hipMemcpyHostToDevice, E.stream), "upload updates");
+    if (len) HIPTRY(E, hipMemcpyAsync(ub.buf, buf, len, hipMemcpyHostToDevice, E.stream), "upload updates");
     if (n)
-        RCHK(hipMemcpyAsync(ub.off, offsets, (n + 1ull) * 8, hipMemcpyHostToDevice, E.stream),
-             "upload offsets");
-    RCHK(hipStreamSynchronize(E.stream), "upload updates");
+        HIPTRY(E, hipMemcpyAsync(ub.off, offsets, (n + 1ull) * 8, hipMemcpyHostToDevice, E.stream),
+                  "upload offsets");
+    HIPTRY(E, hipStreamSynchronize(E.stream), "upload updates");
     ub.len = len;
     ub.n = n;
     // the largest id the batch carries, from its headers (first id, items at words 2, 3); a
@@ -560,7 +548,7 @@ int decode_prepare(Engine& E, Replica& r, uint64_t len, uint32_t n, bool residen
         E.err = "update batch of 4 GiB or more";
         return CRDT_HIP_ERANGE;
     }
-    RCHK(hipSetDevice(E.device), "hipSetDevice");
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     // ids a batch can add: up to its largest id if known, else every item takes at least 16
     // bytes of it
     int rc = replica_reserve(E, r, max_id ? std::max<uint64_t>(r.n, max_id)
@@ -568,27 +556,27 @@ int decode_prepare(Engine& E, Replica& r, uint64_t len, uint32_t n, bool residen
     if (rc) return rc;
     const uint64_t g0 = grow_gen;
     const uint32_t nblk = (n + kUB - 1) / kUB;
-    if (!resident) RCHK(grow(&r.ubuf, r.ubuf_cap, (len + 4) & ~3ull), "hipMalloc update buffer");
+    if (!resident) HIPTRY(E, grow(&r.ubuf, r.ubuf_cap, (len + 4) & ~3ull), "hipMalloc update buffer");
     if (n + 1ull > r.ucap) {
         dfree(r.uoff); dfree(r.uhdr); dfree(r.uscan);
         r.ucap = 0;
         const uint64_t c = std::max<uint64_t>(n + 1ull, 1024);
-        RCHK(dalloc(&r.uoff, c), "hipMalloc update offsets");
-        RCHK(dalloc(&r.uhdr, c), "hipMalloc update headers");
-        RCHK(dalloc(&r.uscan, c), "hipMalloc update scan");
+        HIPTRY(E, dalloc(&r.uoff, c), "hipMalloc update offsets");
+        HIPTRY(E, dalloc(&r.uhdr, c), "hipMalloc update headers");
+        HIPTRY(E, dalloc(&r.uscan, c), "hipMalloc update scan");
         r.ucap = c;
         r.gen++;
     }
-    RCHK(grow(&r.ublk, r.ublk_cap, (uint64_t)nblk), "hipMalloc update blocks");
+    HIPTRY(E, grow(&r.ublk, r.ublk_cap, (uint64_t)nblk), "hipMalloc update blocks");
     // every item takes at least 16 bytes of the batch, every delete 4
-    RCHK(grow(&r.imap, r.imap_cap, len / 16 + 1), "hipMalloc item map");
-    RCHK(grow(&r.dmap, r.dmap_cap, len / 4 + 1), "hipMalloc delete map");
+    HIPTRY(E, grow(&r.imap, r.imap_cap, len / 16 + 1), "hipMalloc item map");
+    HIPTRY(E, grow(&r.dmap, r.dmap_cap, len / 4 + 1), "hipMalloc delete map");
     if (!r.uctl) {
-        RCHK(dalloc(&r.uctl, (uint64_t)U_N), "hipMalloc update counters");
+        HIPTRY(E, dalloc(&r.uctl, (uint64_t)U_N), "hipMalloc update counters");
         r.gen++;
     }
     if (!r.hctl) {
-        RCHK(pool_alloc(reinterpret_cast<void**>(&r.hctl), U_N * 8, true), "hipHostMalloc");
+        HIPTRY(E, pool_alloc(reinterpret_cast<void**>(&r.hctl), U_N * 8, true), "hipHostMalloc");
         r.gen++;
     }
     if (grow_gen != g0) r.gen++;
@@ -618,11 +606,11 @@ int decode_launch(Engine& E, Replica& r, const uint8_t* buf, uint64_t len,
     hipStream_t s = E.stream;
     const uint32_t nblk = (n + kUB - 1) / kUB;
     if (!resident) {
-        RCHK(hipMemcpyAsync(r.ubuf, buf, len, hipMemcpyHostToDevice, s), "upload updates");
-        RCHK(hipMemcpyAsync(r.uoff, offsets, (n + 1ull) * 8, hipMemcpyHostToDevice, s),
-             "upload update offsets");
+        HIPTRY(E, hipMemcpyAsync(r.ubuf, buf, len, hipMemcpyHostToDevice, s), "upload updates");
+        HIPTRY(E, hipMemcpyAsync(r.uoff, offsets, (n + 1ull) * 8, hipMemcpyHostToDevice, s),
+                  "upload update offsets");
     }
-    RCHK(hipMemsetAsync(r.uctl, 0, U_N * 8, s), "memset update counters");
+    HIPTRY(E, hipMemsetAsync(r.uctl, 0, U_N * 8, s), "memset update counters");
     DeviceLogs& L = r.logs;
     UpdArgs a{};
     a.buf = reinterpret_cast<const uint32_t*>(resident ? buf : r.ubuf);
@@ -651,16 +639,16 @@ int decode_launch(Engine& E, Replica& r, const uint8_t* buf, uint64_t len,
     k_upd_dels<false><<<gd, kUB, 0, s>>>(a);
     k_upd_items<true><<<gi, kUB, 0, s>>>(a);
     k_upd_dels<true><<<gd, kUB, 0, s>>>(a);
-    RCHK(hipGetLastError(), "update kernels");
+    HIPTRY(E, hipGetLastError(), "update kernels");
     if (copy_counters)
-        RCHK(hipMemcpyAsync(r.hctl, r.uctl, U_N * 8, hipMemcpyDeviceToHost, s), "copy update counters");
+        HIPTRY(E, hipMemcpyAsync(r.hctl, r.uctl, U_N * 8, hipMemcpyDeviceToHost, s), "copy update counters");
     r.pending = true;
     return CRDT_HIP_OK;
 }
 
 int replica_settle(Engine& E, Replica& r) {
     if (!r.pending && r.graveyard.empty()) return CRDT_HIP_OK;
-    RCHK(hipStreamSynchronize(E.stream), "update sync");
+    HIPTRY(E, hipStreamSynchronize(E.stream), "update sync");
     for (void* p : r.graveyard) pool_free(p, false, true);
     r.graveyard.clear();
     if (!r.pending) return CRDT_HIP_OK;
@@ -764,7 +752,7 @@ int replica_replay(Engine& E, const Replica& init, const UpdateBatch& ub, Replay
             hipStream_t s = E.stream;
             if (key != st.key || !st.exec) {
                 drop_graph(st);
-                RCHK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed), "begin capture");
+                HIPTRY(E, hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed), "begin capture");
                 rc = CRDT_HIP_OK;
                 if (cap) {
                     const DeviceLogs& S = init.logs;
@@ -778,7 +766,7 @@ int replica_replay(Engine& E, const Replica& init, const UpdateBatch& ub, Replay
                                                     b_plan);
                     if (hipMemcpyAsync(w.hctl, w.uctl, U_N * 8, hipMemcpyDeviceToHost, s) !=
                         hipSuccess)
-                        rc = hip_fail(E, "copy update counters", hipGetLastError());
+                        rc = E.fail("copy update counters", hipGetLastError());
                 }
                 if (!rc) rc = E.nsq_launch(w.logs);  // (the decoded contents' nsq list)
                 if (!rc) rc = E.merge_async_enqueue(w.logs, m);
@@ -789,14 +777,14 @@ int replica_replay(Engine& E, const Replica& init, const UpdateBatch& ub, Replay
                     w.pending = false;
                     return rc;
                 }
-                if (ce != hipSuccess) return hip_fail(E, "end capture", ce);
+                if (ce != hipSuccess) return E.fail("end capture", ce);
                 st.graph = g;
-                RCHK(hipGraphInstantiate(&st.exec, g, nullptr, nullptr, 0), "graph instantiate");
+                HIPTRY(E, hipGraphInstantiate(&st.exec, g, nullptr, nullptr, 0), "graph instantiate");
                 st.key = key;
             }
             w.pending = true;  // the graph holds the decode
-            RCHK(hipGraphLaunch(st.exec, s), "graph launch");
-            RCHK(hipStreamSynchronize(s), "replay sync");
+            HIPTRY(E, hipGraphLaunch(st.exec, s), "graph launch");
+            HIPTRY(E, hipStreamSynchronize(s), "replay sync");
             w.vis_cp = init.vis_cp;
             w.vis_bytes = init.vis_bytes;
             uint64_t c1 = 0, b1 = 0, d1 = 0;

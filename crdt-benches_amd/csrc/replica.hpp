@@ -203,7 +203,6 @@ int replica_apply_diff(Engine& E, Replica& dst, const uint8_t* buf, size_t len, 
 
 // Patches since a mark (patch.hip; semantics in crdt_hip.h, host twin OpLog::patches_since): what
 // changed in the replica's document between a mark and now, as positional edits.
-constexpr uint32_t kPatchTile = 4096;  // consecutive ranks of the document order per workgroup
 // A version of one replica: its item count and a device bit plane of n + 1 bits, 1 = the slot was
 // tombstoned or is not an item (slot 0, and the padding of the last word).  Owns the buffer.
 struct DeviceMark {
@@ -250,6 +249,15 @@ struct EditStats {  // what the last device apply_patches observed (crdt_hip_edi
 int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, const uint8_t* ins,
                           size_t ins_len, uint32_t* added, uint32_t* tombstoned,
                           EditStats* stats = nullptr);
+
+// The document order of every item r holds, as a merge_inc leaves it (and leaving r as a merge_inc
+// does): *seq = rank -> slot for ranks 0..n, *ntiles = its tiles of kOrderTile ranks (order.hpp).
+// Checked here, once, for the kernels that stream it: the order covers exactly the replica's
+// items and both it and the slot arrays hold n + 1 entries, so a uint4 load of four ranks at or
+// below n and the gather of their slots stay inside.  EBADLOG "<who>: the kept document order
+// does not cover the replica" otherwise.
+int replica_kept_order(Engine& E, Replica& r, const char* who, const uint32_t** seq,
+                       uint32_t* ntiles);
 
 // Incremental merge (incr.hip): the merged text (may be null), its UTF-8 bytes and codepoints;
 // *path = 1 when only the items appended since the previous merge_inc were ranked, 0 for a

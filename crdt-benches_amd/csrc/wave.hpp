@@ -1,9 +1,12 @@
-// wave.hpp — wave64 / workgroup primitives shared by the gfx950 kernels (engine.hip,
-// replica.hip).  Header-only, internal linkage.
+// wave.hpp — wave64 / workgroup primitives shared by the gfx950 kernels (every .hip file), and
+// what their host sides share: device memory, and the scratch of one call (CallScratch: transient
+// arrays, counters with their pinned copy, the event pair that times the kernels).  Header-only,
+// internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 #include "util.hpp"
 
@@ -48,6 +51,29 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* lds, u
     return off + inc - x;
 }
 
+// One workgroup of NT threads: the counts in[0..m) -> their exclusive prefixes out[0..m) (out may
+// be in), in rounds of NT with the carry of the rounds before; returns the total in every thread.
+// lds: NT / 64 entries.  A prefix is stored as u32: a caller whose total may pass 2^32 compares the
+// returned one.
+template <int NT>
+__device__ __forceinline__ uint64_t block_scan_counts(const uint32_t* in, uint32_t* out, uint32_t m,
+                                                      uint32_t* lds) {
+    uint64_t c = 0;
+    for (uint32_t base = 0; base < m; base += NT) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t x = i < m ? in[i] : 0u;
+        uint32_t t;
+        const uint32_t e = block_excl_scan<NT / 64>(x, lds, t);
+        if (i < m) out[i] = (uint32_t)c + e;
+        c += t;
+    }
+    return c;
+}
+template <int NT>
+__device__ __forceinline__ uint64_t block_scan_counts(uint32_t* v, uint32_t m, uint32_t* lds) {
+    return block_scan_counts<NT>(v, v, m, lds);
+}
+
 // Sum of x over the block's threads (NW waves), valid in thread 0 (a device-wide counter then
 // takes one atomic per block: thousands of same-address atomics, one per wave, serialise at the
 // L2 and cost more than the kernels that count with them).
@@ -82,6 +108,57 @@ void dfree(T*& p) {
 inline uint32_t grid_for(uint64_t n, uint32_t block = 256) {
     return (uint32_t)((n + block - 1) / block);
 }
+
+// One call's transient device arrays, its counters and the events around its kernels, released
+// after a wait for the stream.
+struct CallScratch {
+    hipStream_t stream;
+    std::vector<void*> dev;
+    uint64_t* ctl = nullptr;   // device counters
+    uint64_t* hctl = nullptr;  // pinned host copy
+    hipEvent_t ev[2] = {nullptr, nullptr};  // around each group of kernels
+    uint64_t dev_ns = 0;                    // their summed device time
+    explicit CallScratch(hipStream_t s) : stream(s) {}
+    CallScratch(const CallScratch&) = delete;
+    CallScratch& operator=(const CallScratch&) = delete;
+    template <class T>
+    hipError_t alloc(T** p, uint64_t count) {
+        const hipError_t rc = dalloc(p, count);
+        if (rc == hipSuccess) dev.push_back(*p);
+        return rc;
+    }
+    hipError_t counters(uint32_t n) {
+        hipError_t rc = dalloc(&ctl, (uint64_t)n);
+        if (rc == hipSuccess) rc = pool_alloc(reinterpret_cast<void**>(&hctl), n * 8ull, true);
+        return rc;
+    }
+    // Frees the arrays (the caller has waited for the stream); the counters stay.
+    void drop_arrays() {
+        for (void* p : dev) pool_free(p, false, true);
+        dev.clear();
+    }
+    hipError_t time_begin() {
+        for (hipEvent_t& e : ev)
+            if (!e) {
+                const hipError_t rc = hipEventCreate(&e);
+                if (rc != hipSuccess) return rc;
+            }
+        return hipEventRecord(ev[0], stream);
+    }
+    hipError_t time_end() { return hipEventRecord(ev[1], stream); }
+    void time_add() {  // (after a wait for the stream)
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) dev_ns += (uint64_t)(ms * 1e6);
+    }
+    ~CallScratch() {
+        (void)hipStreamSynchronize(stream);
+        drop_arrays();
+        if (ctl) pool_free(ctl, false, true);
+        if (hctl) pool_free(hctl, true);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
 
 }  // namespace
 }  // namespace crdt

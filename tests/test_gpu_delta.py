@@ -17,6 +17,7 @@ import pytest
 import crdt_hip
 import delta_util as du
 import join_fugue_util as jf
+from edit_util import ALPHABET
 from join_util import (assert_same_log, assert_unique_identities, base_log, fork, to_anchor,
                        visible)
 from test_delta import fugue_rejections, rejections
@@ -170,6 +171,36 @@ def test_apply_equals_the_union_slot_for_slot(ctx, mk, oracle, forks, big, ffork
         assert up.merge() == dst.merge() and up.info() == dst.info()
     finally:
         ctx.set_param("contraction", 0)
+
+
+def test_past_1024_block_counts(mk):
+    """262,444 items are 1,026 blocks of 256: the one-workgroup scans of the block counts take a
+    second round of 1,024 with the carry of the first, in the encode (items, range heads and ends)
+    and in the apply (new items).  Slots 262,201..262,430 are tombstoned: blocks 1,024 and 1,025.
+    Device against the host twin, byte for byte."""
+    n = 262144 + 300
+    text = (ALPHABET * (n // len(ALPHABET) + 1))[:n]
+    live = crdt_hip.OpLog()
+    live.insert(0, text)
+    log = live.clone()
+    log.remove(262200, 262430)
+    whole = log.encode_diff([])
+    rep = mk(log)
+    assert rep.encode_diff([]) == whole
+    # against the vector of the same items: nothing but the range, its head and end past block 1,024
+    ranges = log.encode_diff(live.state_vector())
+    assert du.decode_diff(ranges)["n"] == 0 and list(du.decode_diff(ranges)["rcount"]) == [230]
+    assert rep.encode_diff(live.state_vector()) == ranges
+    first = crdt_hip.OpLog()
+    first.insert(0, text[:100])
+    for held in (crdt_hip.OpLog(), first):
+        k = held.view().n
+        dst = mk(held if k else None)
+        assert dst.apply_diff(whole) == held.apply_diff(whole) == (n - k, 0)
+        assert dst.encode_diff([]) == held.encode_diff([]) == whole
+    dst = mk(live)
+    assert dst.apply_diff(ranges) == live.apply_diff(ranges) == (0, 230)
+    assert dst.encode_diff([]) == live.encode_diff([]) == whole
 
 
 def test_device_and_host_deltas_cross(mk, oracle, forks, fforks):

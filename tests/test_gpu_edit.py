@@ -149,6 +149,29 @@ def test_round_trip_with_patches_since(pair, kind):
     assert t.text == t.ctx.merge(fork)[0].decode("utf-8")
 
 
+@pytest.mark.parametrize("kind", KINDS)
+def test_257_tiles(ctx, kind):
+    """Ranks 0..1,048,700 are 257 tiles: k_edit_top scans the tile counts in two rounds of 256, and
+    the last patch lies in tile 256, the first of the second round, whose visible ranks need the
+    carry of the first.  Device against the host twin slot for slot, and the round trip through
+    patches_since byte for byte."""
+    fugue = kind == "fugue"
+    plist = [(5, 2, "Q"), (4095, 3, ""), (1_048_600, 0, "tail")]
+    host = typed(fugue, (eu.ALPHABET * (1_048_700 // len(eu.ALPHABET) + 1))[:1_048_700])
+    rep = crdt_hip.Replica(ctx, host)
+    try:
+        dm, hm = rep.mark(), host.mark()
+        assert rep.apply_patches(plist) == host.apply_patches(plist) == (5, 5)
+        s = ctx.edit_stats()
+        assert (s["patches"], s["items"], s["tombstones"], s["ranks"]) == (3, 5, 5, 1_048_700)
+        assert rep.encode_diff([]) == host.encode_diff([])
+        raw = rep.patches_since_raw(dm)
+        assert pu.same_raw(raw, host.patches_since_raw(hm))
+        assert crdt_hip._patch_list(raw) == plist
+    finally:
+        rep.close()
+
+
 def dead(log: crdt_hip.OpLog, first: int, last: int) -> None:
     """Tombstones the items of ranks first..last of a log typed in one piece and not edited since
     (rank k = item k), given that every rank below `first` is still visible."""

@@ -13,6 +13,7 @@ import pytest
 
 import crdt_hip
 from conftest import trace_path
+from edit_util import ALPHABET
 from join_util import (assert_same_log, assert_unique_identities, base_log, crafted, fork,
                        random_edits, to_anchor, union, visible)
 import random
@@ -91,6 +92,28 @@ def forks():
     c = fork(base, 3, 33, 60)
     assert_unique_identities(a.arrays(), b.arrays(), c.arrays())
     return base, nb, a, b, c
+
+
+def test_more_than_262144_new_items(ctx, mk):
+    """262,400 src slots past the prefix are 1,025 blocks of 256: k_join_top scans the block counts
+    in two rounds of 1,024, the second with the carry of the first.  Device against the host join,
+    slot for slot (the log read back as a delta against the empty vector)."""
+    base = crdt_hip.OpLog()
+    base.insert(0, (ALPHABET * 7)[:200])
+    a, b = base.clone(), base.clone()
+    a.set_agent(1)
+    b.set_agent(2)
+    a.insert(200, (ALPHABET * 2)[:50])
+    b.insert(100, (ALPHABET * (262400 // len(ALPHABET) + 1))[:262400])
+    for dst, src in ((a, b), (b, a)):
+        want = dst.clone()
+        added = want.join(src)
+        assert added == (src.view().n - 200, 0)
+        rd, rs = mk(dst), mk(src)
+        assert rd.join(rs) == added
+        assert ctx.join_stats()["prefix_slots"] == 200
+        assert rd.encode_diff([]) == want.encode_diff([])
+        assert rd.info()[0] == 200 + 50 + 262400
 
 
 @pytest.mark.parametrize("contraction", [1, 2])

@@ -20,6 +20,7 @@ import delta_util as du
 import join_fugue_util as jf
 import join_util as ju
 import patch_util as pu
+from edit_util import ALPHABET
 from test_gpu_replica import trace_updates
 from test_patches import KINDS, TEXT, forks_of, typed
 
@@ -95,6 +96,31 @@ def twin(ctx, oracle):
     yield make
     for t in made:
         t.close()
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_257_tiles(ctx, kind):
+    """Ranks 0..1,048,705 are 257 tiles: k_patch_top scans the tile aggregates in two rounds of
+    256, and the last patch lies in tile 256, the first of the second round, whose position needs
+    the carry of the first.  The edits arrive as one wire update; device against the host twin, the
+    patch array and the bytes."""
+    fugue = kind == "fugue"
+    plist = [(5, 2, "Q"), (4095, 3, ""), (1_048_600, 0, "tail")]
+    host = typed(fugue, (ALPHABET * (1_048_700 // len(ALPHABET) + 1))[:1_048_700])
+    rep = crdt_hip.Replica(ctx, host)
+    try:
+        dm, hm = rep.mark(), host.mark()
+        v = host.version()
+        assert host.apply_patches(plist) == (5, 5)
+        rep.apply_updates([host.encode_from(v)])
+        raw = rep.patches_since_raw(dm)
+        assert pu.same_raw(raw, host.patches_since_raw(hm))
+        assert crdt_hip._patch_list(raw) == plist
+        s = ctx.patch_stats()
+        assert (s["patches"], s["ins_bytes"], s["ranks"]) == (3, 5, 1_048_705)
+        assert rep.encode_diff([]) == host.encode_diff([])
+    finally:
+        rep.close()
 
 
 @pytest.mark.parametrize("kind", KINDS)
