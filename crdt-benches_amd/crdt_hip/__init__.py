@@ -29,6 +29,10 @@ STAGES = ["classify", "runs", "sortb", "count", "scan", "place", "link", "walk1"
 
 # Every symbol include/crdt_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = [
+    "crdt_hip_oplog_visible_bytes", "crdt_hip_oplog_apply_patches_bytes",
+    "crdt_hip_oplog_replace_bytes", "crdt_hip_oplog_patches_since_bytes",
+    "crdt_hip_replica_apply_patches_bytes", "crdt_hip_replica_replace_bytes",
+    "crdt_hip_replica_patches_since_bytes",
     "crdt_hip_abi_version", "crdt_hip_device_count", "crdt_hip_init", "crdt_hip_destroy",
     "crdt_hip_last_error", "crdt_hip_set_param", "crdt_hip_oplog_new", "crdt_hip_oplog_set_fugue",
     "crdt_hip_oplog_set_agent", "crdt_hip_oplog_clone", "crdt_hip_trace_resolve_fugue",
@@ -194,6 +198,13 @@ def lib() -> C.CDLL:
         "crdt_hip_replica_apply_patches": (i32, [vp, vp, vp, sz, vp, sz, P(u32), P(u32)]),
         "crdt_hip_replica_replace": (i32, [vp, vp, sz, sz, C.c_char_p, sz]),
         "crdt_hip_edit_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64), P(u64)]),
+        "crdt_hip_oplog_visible_bytes": (i32, [vp, P(u64)]),
+        "crdt_hip_oplog_apply_patches_bytes": (i32, [vp, vp, sz, vp, sz, P(u32), P(u32)]),
+        "crdt_hip_oplog_replace_bytes": (i32, [vp, sz, sz, C.c_char_p, sz]),
+        "crdt_hip_oplog_patches_since_bytes": (i32, [vp, vp, vp, sz, P(sz), vp, sz, P(sz)]),
+        "crdt_hip_replica_apply_patches_bytes": (i32, [vp, vp, vp, sz, vp, sz, P(u32), P(u32)]),
+        "crdt_hip_replica_replace_bytes": (i32, [vp, vp, sz, sz, C.c_char_p, sz]),
+        "crdt_hip_replica_patches_since_bytes": (i32, [vp, vp, vp, vp, sz, P(sz), vp, sz, P(sz)]),
         "crdt_hip_replica_merge": (i32, [vp, vp, vp, sz, P(sz), P(u64)]),
         "crdt_hip_replica_merge_len": (i32, [vp, vp, P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge_inc": (i32, [vp, vp, vp, sz, P(sz), P(u64), P(u32)]),
@@ -536,6 +547,47 @@ class OpLog:
             self._h, arr.ctypes.data if arr.size else None, arr.size, text, len(text),
             C.byref(a), C.byref(t)))
         return int(a.value), int(t.value)
+
+    # Byte offsets (crdt_hip.h, "byte offsets"): the same calls with pos and del in UTF-8 bytes of
+    # the visible document.  The host calls are the definition the device calls are held to; a call
+    # walks the whole document.
+    def visible_bytes(self) -> int:
+        """UTF-8 bytes of the visible document (crdt_hip_oplog_visible_bytes)."""
+        b = C.c_uint64()
+        _check(lib().crdt_hip_oplog_visible_bytes(self._h, C.byref(b)))
+        return int(b.value)
+
+    def apply_patches_bytes(self, patches, ins=None) -> tuple:
+        """apply_patches with pos and del in UTF-8 bytes (crdt_hip_oplog_apply_patches_bytes): the
+        log apply_patches gives for the patches translated through the text before the call.  A
+        boundary inside a codepoint raises EINVAL.  Returns (items appended, items deleted)."""
+        arr, text = _patches_pack(patches, ins)
+        a, t = C.c_uint32(), C.c_uint32()
+        _check(lib().crdt_hip_oplog_apply_patches_bytes(
+            self._h, arr.ctypes.data if arr.size else None, arr.size, text, len(text),
+            C.byref(a), C.byref(t)))
+        return int(a.value), int(t.value)
+
+    def replace_bytes(self, start: int, end: int, text: str) -> None:
+        b = text.encode("utf-8")
+        _check(lib().crdt_hip_oplog_replace_bytes(self._h, start, end, b, len(b)))
+
+    def insert_bytes(self, pos: int, text: str) -> None:
+        self.replace_bytes(pos, pos, text)
+
+    def remove_bytes(self, start: int, end: int) -> None:
+        if end < start:
+            raise CrdtHipError(-2, "remove range out of range")
+        self.replace_bytes(start, end, "")
+
+    def patches_since_bytes_raw(self, mark: Mark) -> tuple:
+        return _patches_get(lambda *a: lib().crdt_hip_oplog_patches_since_bytes(
+            self._h, mark._h, *a))
+
+    def patches_since_bytes(self, mark: Mark) -> list:
+        """patches_since with pos and del in UTF-8 bytes: spliced in order into the UTF-8 of the
+        text at the mark they give the UTF-8 now (crdt_hip_oplog_patches_since_bytes)."""
+        return _patch_list(self.patches_since_bytes_raw(mark))
 
     def save(self, path: str) -> None:
         """Op-log file (crdt_hip_oplog_save): 64-byte-aligned SoA arrays."""
@@ -1020,6 +1072,43 @@ class Replica:
             raise CrdtHipError(-2, "remove range out of range")
         self.replace(start, end, "")
 
+    # Byte offsets (crdt_hip.h, "byte offsets"): the boundaries are translated to codepoint ranks
+    # in HIP kernels against the kept order; no text is kept on the host.
+    def apply_patches_bytes(self, patches, ins=None) -> tuple:
+        """OpLog.apply_patches_bytes on the device (crdt_hip_replica_apply_patches_bytes): the same
+        resulting log, slot for slot.  Returns (items appended, items deleted); a rejected call
+        raises and changes nothing."""
+        arr, text = _patches_pack(patches, ins)
+        a, t = C.c_uint32(), C.c_uint32()
+        _check(lib().crdt_hip_replica_apply_patches_bytes(
+            self.ctx._h, self._h, arr.ctypes.data if arr.size else None, arr.size, text, len(text),
+            C.byref(a), C.byref(t)), self.ctx._h)
+        return int(a.value), int(t.value)
+
+    def replace_bytes(self, start: int, end: int, text: str) -> None:
+        """Upstream::replace in byte offsets on the device (crdt_hip_replica_replace_bytes)."""
+        b = text.encode("utf-8")
+        _check(lib().crdt_hip_replica_replace_bytes(self.ctx._h, self._h, start, end, b, len(b)),
+               self.ctx._h)
+
+    def insert_bytes(self, pos: int, text: str) -> None:
+        self.replace_bytes(pos, pos, text)
+
+    def remove_bytes(self, start: int, end: int) -> None:
+        if end < start:
+            raise CrdtHipError(-2, "remove range out of range")
+        self.replace_bytes(start, end, "")
+
+    def patches_since_bytes_raw(self, mark: Mark) -> tuple:
+        """(crdt_hip_patch array as a structured numpy array, `ins` bytes) of
+        crdt_hip_replica_patches_since_bytes."""
+        return _patches_get(lambda *a: lib().crdt_hip_replica_patches_since_bytes(
+            self.ctx._h, self._h, mark._h, *a), self.ctx._h, guess=(4096, 1 << 16))
+
+    def patches_since_bytes(self, mark: Mark) -> list:
+        """OpLog.patches_since_bytes on the device: the same patches."""
+        return _patch_list(self.patches_since_bytes_raw(mark))
+
     def info(self) -> tuple:
         """(items, visible codepoints, visible UTF-8 bytes)."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -1275,3 +1364,44 @@ class HipDownstream:
         if cps != counter:
             raise CrdtHipError(-5, f"merged text has {cps} codepoints, the decoder counted {counter}")
         return cps
+
+
+class HipDownstreamBytes(HipDownstream):
+    """HipDownstream for a caller that keeps its text as UTF-8 (EDITS_USE_BYTE_OFFSETS = true,
+    rope.rs:8,16-19, as the cola and yrs adapters): insert, remove and replace take byte offsets,
+    patches_since and sync_patches return byte patches, and len() is a byte length.  The offsets
+    are translated on the device (crdt_hip.h, "byte offsets"); no text is kept on the host."""
+
+    NAME = "mi355x-device-bytes"
+    EDITS_USE_BYTE_OFFSETS = True
+
+    def insert(self, at: int, text: str) -> None:
+        self.flush()
+        self.replica.insert_bytes(at, text)
+
+    def remove(self, start: int, end: int) -> None:
+        self.flush()
+        self.replica.remove_bytes(start, end)
+
+    def replace(self, start: int, end: int, text: str) -> None:
+        self.flush()
+        self.replica.replace_bytes(start, end, text)
+
+    def clone(self) -> "HipDownstreamBytes":
+        c = HipDownstreamBytes(self.replica.clone())
+        c.pending = list(self.pending)
+        return c
+
+    def patches_since(self, mark: Mark) -> list:
+        self.flush()
+        return self.replica.patches_since_bytes(mark)
+
+    def len(self) -> int:
+        """UTF-8 bytes of the merged document: the merge's own count, cross-checked against the
+        decoder's visible-byte counter."""
+        self.flush()
+        _, nbytes, _ = self.replica.merge_len()
+        counter = self.replica.info()[2]
+        if nbytes != counter:
+            raise CrdtHipError(-5, f"merged text has {nbytes} bytes, the decoder counted {counter}")
+        return nbytes

@@ -1,0 +1,40 @@
+// bytes.hpp — what edit.hip hands to the translation kernels of bytes.hip: byte-offset patches
+// (crdt_hip.h, "byte offsets") turned into the codepoint patch table k_edit_resolve and
+// k_edit_emit take, where the replica lies.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "oplog.hpp"
+
+namespace crdt {
+
+// device counters (u64) of a translation
+enum BCtl { B_ERR = 0, B_VIS, B_VISB, B_STARTS, B_ENDS, B_NDEL, B_N };
+// B_ERR bits
+constexpr uint64_t EB_SLOT = 1;   // the order names a slot that is no item of the replica
+constexpr uint64_t EB_TABLE = 2;  // a patch whose end was found before its start
+
+// Device pointers only; the caller (replica_apply_patches_bytes) owns every array.
+struct BytesArgs {
+    const uint32_t* seq;     // rank -> slot, ranks 0..n (replica_kept_order)
+    const uint8_t* cp;       // 3-byte codepoint words of slots 0..n
+    uint32_t n;              // items held
+    uint32_t ntiles;         // tiles of kOrderTile ranks
+    uint32_t* tcount;        // per tile: visible items, then their exclusive prefix
+    uint32_t* tbytes;        // per tile: visible UTF-8 bytes (at most 16 KiB)
+    uint64_t* tbpre;         //   and their exclusive prefix, which may pass 2^32
+    const BytePatch* btab;   // the patches in bytes, by old byte position
+    uint32_t np;
+    uint32_t* cp_start;      // per patch: visible items before it (NIL: no item ends there)
+    uint32_t* cp_end;        //   and before the end of its delete range
+    EditPatch* tab;          // out: the table in codepoints, del0 filled in
+    uint64_t* ctl;           // B_N counters
+};
+
+// Enqueues the translation on `s`: init, count, top, translate, table.  The caller then waits
+// for ctl: B_STARTS or B_ENDS below np means a boundary inside a codepoint.
+void bytes_translate_enqueue(const BytesArgs& a, hipStream_t s);
+
+}  // namespace crdt

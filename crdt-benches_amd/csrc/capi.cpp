@@ -133,6 +133,16 @@ int stage_views(crdt_hip_ctx* ctx, const crdt_hip_oplog_view* logs, uint32_t n) 
     if (rc) return from_engine(ctx, rc);
     return from_engine(ctx, ctx->eng.upload(ctx->staging, logs, n));
 }
+// Upstream::replace (rope.rs:21-32) as one patch; `what` applies it.  0 for the empty replace.
+template <class Apply>
+int replace_as_patch(crdt_hip_ctx* ctx, size_t start, size_t end, size_t nbytes, Apply&& what) {
+    const size_t del = end > start ? end - start : 0;
+    if (del == 0 && nbytes == 0) return 0;
+    if (del > 0xFFFFFFFFull || nbytes > 0xFFFFFFFFull)
+        return set_err(ctx, CRDT_HIP_ERANGE, "replace of 2^32 or more bytes");
+    const crdt_hip_patch one{(uint64_t)start, 0, (uint32_t)del, (uint32_t)nbytes};
+    return what(&one);
+}
 }  // namespace
 
 extern "C" {
@@ -353,6 +363,11 @@ int crdt_hip_oplog_replace(crdt_hip_oplog* log, size_t start, size_t end, const 
     return 0;
 }
 size_t crdt_hip_oplog_visible_len(const crdt_hip_oplog* log) { return log ? log->log.visible() : 0; }
+int crdt_hip_oplog_visible_bytes(const crdt_hip_oplog* log, uint64_t* out) {
+    if (!log || !out) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    *out = log->log.visible_bytes();
+    return 0;
+}
 
 int crdt_hip_oplog_get_view(const crdt_hip_oplog* log, crdt_hip_oplog_view* out) {
     if (!log || !out) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
@@ -1101,6 +1116,82 @@ int crdt_hip_edit_stats(const crdt_hip_ctx* ctx, uint64_t* patches, uint64_t* it
     if (ranks) *ranks = ctx->last_edit.ranks;
     if (device_ns) *device_ns = ctx->last_edit.device_ns;
     return 0;
+}
+// ---- byte offsets: the same patches with pos and del in UTF-8 bytes ---------------------------------
+int crdt_hip_oplog_apply_patches_bytes(crdt_hip_oplog* log, const crdt_hip_patch* p, size_t n,
+                                       const uint8_t* ins, size_t ins_len, uint32_t* added,
+                                       uint32_t* tombstoned) {
+    if (!log || (!p && n) || (!ins && ins_len)) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    return guard(nullptr, [&] {
+        std::string e;
+        const int rc = log->log.apply_patches_bytes(reinterpret_cast<const crdt::PatchRec*>(p), n,
+                                                    ins, ins_len, added, tombstoned, e);
+        return rc ? set_err(nullptr, rc, e) : 0;
+    });
+}
+int crdt_hip_oplog_replace_bytes(crdt_hip_oplog* log, size_t start, size_t end, const char* utf8,
+                                 size_t nbytes) {
+    if (!log || (!utf8 && nbytes)) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    return replace_as_patch(nullptr, start, end, nbytes, [&](const crdt_hip_patch* one) {
+        return crdt_hip_oplog_apply_patches_bytes(log, one, 1, reinterpret_cast<const uint8_t*>(utf8),
+                                                  nbytes, nullptr, nullptr);
+    });
+}
+int crdt_hip_oplog_patches_since_bytes(crdt_hip_oplog* log, const crdt_hip_mark* m,
+                                       crdt_hip_patch* out, size_t cap, size_t* out_n, uint8_t* ins,
+                                       size_t ins_cap, size_t* out_ins) {
+    if (!log || !m || !out_n || !out_ins) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    if (m->ctx) return set_err(nullptr, CRDT_HIP_EINVAL, "a replica's mark passed to a log");
+    if (m->owner != log->uid) return set_err(nullptr, CRDT_HIP_EINVAL, "the mark belongs to another log");
+    return guard(nullptr, [&] {
+        std::vector<crdt::PatchRec> p;
+        std::vector<uint8_t> text;
+        std::string e;
+        const int rc = log->log.patches_since_bytes(m->host, p, text, e);
+        if (rc) return set_err(nullptr, rc, e);
+        *out_n = p.size();
+        *out_ins = text.size();
+        if ((!p.empty() && (!out || cap < p.size())) || (!text.empty() && (!ins || ins_cap < text.size())))
+            return set_err(nullptr, CRDT_HIP_ESPACE, "buffer too small");
+        if (!p.empty()) std::memcpy(out, p.data(), p.size() * sizeof(crdt::PatchRec));
+        if (!text.empty()) std::memcpy(ins, text.data(), text.size());
+        return 0;
+    });
+}
+int crdt_hip_replica_apply_patches_bytes(crdt_hip_ctx* ctx, crdt_hip_replica* r,
+                                         const crdt_hip_patch* p, size_t n, const uint8_t* ins,
+                                         size_t ins_len, uint32_t* added, uint32_t* tombstoned) {
+    if (!ctx || !r || (!p && n) || (!ins && ins_len)) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    return guard(ctx, [&] {
+        return from_engine(ctx, crdt::replica_apply_patches_bytes(
+                                    ctx->eng, r->r, reinterpret_cast<const crdt::PatchRec*>(p), n, ins,
+                                    ins_len, added, tombstoned, &ctx->last_edit));
+    });
+}
+int crdt_hip_replica_replace_bytes(crdt_hip_ctx* ctx, crdt_hip_replica* r, size_t start, size_t end,
+                                   const char* utf8, size_t nbytes) {
+    if (!ctx || !r || (!utf8 && nbytes)) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    return replace_as_patch(ctx, start, end, nbytes, [&](const crdt_hip_patch* one) {
+        return crdt_hip_replica_apply_patches_bytes(
+            ctx, r, one, 1, reinterpret_cast<const uint8_t*>(utf8), nbytes, nullptr, nullptr);
+    });
+}
+int crdt_hip_replica_patches_since_bytes(crdt_hip_ctx* ctx, crdt_hip_replica* r,
+                                         const crdt_hip_mark* m, crdt_hip_patch* out, size_t cap,
+                                         size_t* out_n, uint8_t* ins, size_t ins_cap,
+                                         size_t* out_ins) {
+    if (!ctx || !r || !m || !out_n || !out_ins) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    if (!m->ctx) return set_err(ctx, CRDT_HIP_EINVAL, "a log's mark passed to a replica");
+    if (m->ctx != ctx || m->owner != r->uid)
+        return set_err(ctx, CRDT_HIP_EINVAL, "the mark belongs to another replica");
+    return guard(ctx, [&] {
+        return from_engine(ctx, crdt::replica_patches_since_bytes(
+                                    ctx->eng, r->r, m->dev, reinterpret_cast<crdt::PatchRec*>(out), cap,
+                                    out_n, ins, ins_cap, out_ins, &ctx->last_patch));
+    });
 }
 int crdt_hip_replica_info(const crdt_hip_replica* r, uint64_t* items,
                           uint64_t* visible_codepoints, uint64_t* visible_bytes) {

@@ -44,12 +44,18 @@
 // The host waits once before the decode, for the counters: the largest lamport (the ERANGE check)
 // and the integrity counts (visible items, anchors found, ids deleted).
 //
+// The byte-offset entry point (crdt_hip_replica_apply_patches_bytes; crdt_hip.h, "byte offsets")
+// shares everything after "the patch table is known" (edit_run): its table is built on the device
+// by the translation kernels of bytes.hip, after which it waits once more (the boundary check and
+// the number of deleted items, which sizes the update).
+//
 // Known cost: a call streams every slot and every rank of the replica, even for one keystroke, and
 // after a join or a delta it also pays inc_rebuild's ORDER-mode merge.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
+#include "bytes.hpp"
 #include "idtab.hpp"
 #include "oplog.hpp"
 #include "order.hpp"
@@ -288,34 +294,21 @@ __global__ __launch_bounds__(kJB) void k_edit_emit(EditArgs a) {
 }  // namespace
 
 // ---- host side ---------------------------------------------------------------------------------
-int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, const uint8_t* ins,
-                          size_t ins_len, uint32_t* added, uint32_t* tombstoned, EditStats* stats) {
-    if (stats) *stats = EditStats{};
-    if (added) *added = 0;
-    if (tombstoned) *tombstoned = 0;
-    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
-    int rc = replica_settle(E, r);
-    if (rc) return rc;
-    if (n == 0) return CRDT_HIP_OK;
-    if (!p) {
-        E.err = "null patch array";
-        return CRDT_HIP_EINVAL;
-    }
-    // everything the arguments and the replica's own counters can tell, before any device work
-    EditPlan plan;
-    rc = edit_plan(p, n, ins, ins_len, r.vis_cp, r.n, plan, E.err);
-    if (rc) return rc;
-    const uint64_t ncp = plan.cps.size(), ndel = plan.ndel, np = plan.patch.size();
-    const uint64_t words = 6 + 4 * ncp + (2 * ncp + 3) / 4 + ndel;
-    if (words * 4 >= (1ull << 32) - 16) {
-        E.err = "edit of 4 GiB or more";
-        return CRDT_HIP_ERANGE;
-    }
+namespace {
+
+// 32-bit words of the update that ncp new items and ndel deleted ids make.
+uint64_t edit_words(uint64_t ncp, uint64_t ndel) { return 6 + 4 * ncp + (2 * ncp + 3) / 4 + ndel; }
+
+// Everything after "the patch table is known": shared by the codepoint entry point, which uploads
+// the table edit_plan made (host_tab), and the byte entry point, whose table bytes.hip built on the
+// device (dev_tab).  a: seq and ntiles set (an empty replica: neither).  cps: every inserted
+// codepoint.  The lamport bound is checked here, after everything else.
+int edit_run(Engine& E, Replica& r, CallScratch& sc, EditArgs& a, const std::vector<uint32_t>& cpsv,
+             const EditPatch* host_tab, EditPatch* dev_tab, uint64_t np, uint64_t ndel,
+             uint32_t* added, uint32_t* tombstoned, EditStats* stats) {
+    const uint64_t ncp = cpsv.size(), words = edit_words(ncp, ndel);
     const bool empty = r.n == 0;
-    EditArgs a{};  // (an empty replica has no order: seq null, no tiles)
-    if (!empty && (rc = replica_kept_order(E, r, "edit", &a.seq, &a.ntiles))) return rc;
-    hipStream_t s = E.stream;
-    CallScratch sc(s);
+    hipStream_t s = sc.stream;
     a.cp = r.logs.cp;
     a.key = r.logs.key;
     a.parent = r.logs.parent;
@@ -327,13 +320,13 @@ int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, co
     a.agent = r.agent;
     a.wire_words = words;
     const uint64_t hasr_words = ((uint64_t)r.n + 32) / 32;
-    EditPatch* tab = nullptr;
+    EditPatch* tab = dev_tab;
     uint32_t* cps = nullptr;
-    HIPTRY(E, sc.counters(E_N), "hipMalloc edit counters");
+    if (!sc.ctl) HIPTRY(E, sc.counters(E_N), "hipMalloc edit counters");
     a.ctl = sc.ctl;
     HIPTRY(E, sc.alloc(&a.tcount, (uint64_t)a.ntiles), "hipMalloc edit tiles");
     HIPTRY(E, sc.alloc(&a.hasr, hasr_words), "hipMalloc edit right-child bits");
-    HIPTRY(E, sc.alloc(&tab, np), "hipMalloc edit patches");
+    if (host_tab) HIPTRY(E, sc.alloc(&tab, np), "hipMalloc edit patches");
     HIPTRY(E, sc.alloc(&a.left, np), "hipMalloc edit anchors");
     HIPTRY(E, sc.alloc(&a.succ, np), "hipMalloc edit anchors");
     HIPTRY(E, sc.alloc(&cps, ncp), "hipMalloc edit codepoints");
@@ -341,10 +334,11 @@ int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, co
     HIPTRY(E, sc.alloc(&a.woff, 2), "hipMalloc edit update");
     a.tab = tab;
     a.cps = cps;
-    // (plan outlives the wait below, so the uploads may read it until then)
-    HIPTRY(E, hipMemcpyAsync(tab, plan.patch.data(), np * sizeof(EditPatch), hipMemcpyHostToDevice, s),
-              "upload edit patches");
-    if (ncp) HIPTRY(E, hipMemcpyAsync(cps, plan.cps.data(), ncp * 4, hipMemcpyHostToDevice, s), "upload edit text");
+    // (the caller's plan outlives the wait below, so the uploads may read it until then)
+    if (host_tab)
+        HIPTRY(E, hipMemcpyAsync(tab, host_tab, np * sizeof(EditPatch), hipMemcpyHostToDevice, s),
+                  "upload edit patches");
+    if (ncp) HIPTRY(E, hipMemcpyAsync(cps, cpsv.data(), ncp * 4, hipMemcpyHostToDevice, s), "upload edit text");
     HIPTRY(E, sc.time_begin(), "edit event");
     k_edit_init<<<grid_for(std::max<uint64_t>(np, E_N), kJB), kJB, 0, s>>>(a, empty ? 1u : 0u);
     if (!empty) {
@@ -386,7 +380,7 @@ int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, co
     const uint32_t n0 = r.n;
     const uint64_t vis0 = r.vis_cp;
     HIPTRY(E, sc.time_begin(), "edit event");
-    rc = replica_decode_enqueue(E, r, reinterpret_cast<const uint8_t*>(a.wire), words * 4, a.woff, 1,
+    int rc = replica_decode_enqueue(E, r, reinterpret_cast<const uint8_t*>(a.wire), words * 4, a.woff, 1,
                                 true, ncp ? (uint32_t)(n0 + ncp) : 0u, true);
     if (rc) return rc;
     HIPTRY(E, sc.time_end(), "edit event");
@@ -407,6 +401,128 @@ int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, co
         stats->device_ns = sc.dev_ns;
     }
     return CRDT_HIP_OK;
+}
+
+}  // namespace
+
+int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, const uint8_t* ins,
+                          size_t ins_len, uint32_t* added, uint32_t* tombstoned, EditStats* stats) {
+    if (stats) *stats = EditStats{};
+    if (added) *added = 0;
+    if (tombstoned) *tombstoned = 0;
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
+    int rc = replica_settle(E, r);
+    if (rc) return rc;
+    if (n == 0) return CRDT_HIP_OK;
+    if (!p) {
+        E.err = "null patch array";
+        return CRDT_HIP_EINVAL;
+    }
+    // everything the arguments and the replica's own counters can tell, before any device work
+    EditPlan plan;
+    rc = edit_plan(p, n, ins, ins_len, r.vis_cp, r.n, plan, E.err);
+    if (rc) return rc;
+    if (edit_words(plan.cps.size(), plan.ndel) * 4 >= (1ull << 32) - 16) {
+        E.err = "edit of 4 GiB or more";
+        return CRDT_HIP_ERANGE;
+    }
+    EditArgs a{};  // (an empty replica has no order: seq null, no tiles)
+    if (r.n != 0 && (rc = replica_kept_order(E, r, "edit", &a.seq, &a.ntiles))) return rc;
+    CallScratch sc(E.stream);
+    return edit_run(E, r, sc, a, plan.cps, plan.patch.data(), nullptr, plan.patch.size(), plan.ndel,
+                    added, tombstoned, stats);
+}
+
+// The byte-offset reading (crdt_hip.h, "byte offsets"): edit_plan_bytes, the translation kernels
+// of bytes.hip, one more wait (the boundary check, and the number of deleted items, which sizes the
+// update), then edit_run on the table the device built.  Two host waits before the decode where
+// the codepoint call makes one.
+int replica_apply_patches_bytes(Engine& E, Replica& r, const PatchRec* p, size_t n,
+                                const uint8_t* ins, size_t ins_len, uint32_t* added,
+                                uint32_t* tombstoned, EditStats* stats) {
+    if (stats) *stats = EditStats{};
+    if (added) *added = 0;
+    if (tombstoned) *tombstoned = 0;
+    HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
+    int rc = replica_settle(E, r);
+    if (rc) return rc;
+    if (n == 0) return CRDT_HIP_OK;
+    if (!p) {
+        E.err = "null patch array";
+        return CRDT_HIP_EINVAL;
+    }
+    EditPlanBytes plan;
+    rc = edit_plan_bytes(p, n, ins, ins_len, r.vis_bytes, r.n, plan, E.err);
+    if (rc) return rc;
+    const uint64_t np = plan.patch.size(), ncp = plan.cps.size();
+    EditArgs a{};
+    if (r.n == 0) {
+        // nothing to translate: the checks left one patch, at byte 0 of an empty document
+        if (np != 1 || plan.patch[0].old_pos_b || plan.patch[0].del_b) {
+            E.err = "edit: a patch set beyond an empty replica passed the checks";
+            return CRDT_HIP_EBADLOG;
+        }
+        if (edit_words(ncp, 0) * 4 >= (1ull << 32) - 16) {
+            E.err = "edit of 4 GiB or more";
+            return CRDT_HIP_ERANGE;
+        }
+        const EditPatch one{0u, 0u, 0u, (uint32_t)ncp, 0u, 0u};
+        CallScratch sc(E.stream);
+        return edit_run(E, r, sc, a, plan.cps, &one, nullptr, 1, 0, added, tombstoned, stats);
+    }
+    if ((rc = replica_kept_order(E, r, "edit", &a.seq, &a.ntiles))) return rc;
+    hipStream_t s = E.stream;
+    CallScratch sc(s);
+    HIPTRY(E, sc.counters(E_N + B_N), "hipMalloc edit counters");
+    BytesArgs b{};
+    b.seq = a.seq;
+    b.cp = r.logs.cp;
+    b.n = r.n;
+    b.ntiles = a.ntiles;
+    b.np = (uint32_t)np;
+    b.ctl = sc.ctl + E_N;
+    BytePatch* btab = nullptr;
+    HIPTRY(E, sc.alloc(&b.tcount, (uint64_t)b.ntiles), "hipMalloc byte tiles");
+    HIPTRY(E, sc.alloc(&b.tbytes, (uint64_t)b.ntiles), "hipMalloc byte tiles");
+    HIPTRY(E, sc.alloc(&b.tbpre, (uint64_t)b.ntiles), "hipMalloc byte tiles");
+    HIPTRY(E, sc.alloc(&btab, np), "hipMalloc byte patches");
+    HIPTRY(E, sc.alloc(&b.cp_start, np), "hipMalloc byte patches");
+    HIPTRY(E, sc.alloc(&b.cp_end, np), "hipMalloc byte patches");
+    HIPTRY(E, sc.alloc(&b.tab, np), "hipMalloc edit patches");
+    b.btab = btab;
+    HIPTRY(E, hipMemcpyAsync(btab, plan.patch.data(), np * sizeof(BytePatch), hipMemcpyHostToDevice, s),
+              "upload byte patches");
+    HIPTRY(E, sc.time_begin(), "edit event");
+    bytes_translate_enqueue(b, s);
+    HIPTRY(E, hipGetLastError(), "byte translation kernels");
+    HIPTRY(E, sc.time_end(), "edit event");
+    HIPTRY(E, hipMemcpyAsync(sc.hctl + E_N, b.ctl, B_N * 8, hipMemcpyDeviceToHost, s), "copy byte counters");
+    HIPTRY(E, hipStreamSynchronize(s), "byte translation sync");  // the wait the byte form adds
+    sc.time_add();
+    const uint64_t* c = sc.hctl + E_N;
+    if (c[B_ERR]) {
+        E.err = c[B_ERR] & EB_SLOT ? "edit: the kept document order names a slot that is no item"
+                                   : "edit: a patch ends before it starts";
+        return CRDT_HIP_EBADLOG;
+    }
+    if (c[B_VIS] != r.vis_cp || c[B_VISB] != r.vis_bytes) {
+        E.err = "edit: the visible bytes of the kept order disagree with the replica's counters";
+        return CRDT_HIP_EBADLOG;
+    }
+    if (c[B_STARTS] < np || c[B_ENDS] < np) {
+        E.err = "patch boundary inside a codepoint";
+        return CRDT_HIP_EINVAL;
+    }
+    const uint64_t ndel = c[B_NDEL];
+    if (c[B_STARTS] != np || c[B_ENDS] != np || ndel > r.vis_cp) {
+        E.err = "edit: the translated patches disagree with the replica's counters";
+        return CRDT_HIP_EBADLOG;
+    }
+    if (edit_words(ncp, ndel) * 4 >= (1ull << 32) - 16) {
+        E.err = "edit of 4 GiB or more";
+        return CRDT_HIP_ERANGE;
+    }
+    return edit_run(E, r, sc, a, plan.cps, nullptr, b.tab, np, ndel, added, tombstoned, stats);
 }
 
 }  // namespace crdt

@@ -286,7 +286,7 @@ public:
             dev_->ctx, 4096, 1 << 16);
     }
 
-private:
+protected:
     std::shared_ptr<Device> dev_;
     crdt_hip_replica* rep_ = nullptr;
     mutable std::vector<uint8_t> buf_;
@@ -300,6 +300,45 @@ private:
               dev_->ctx, "replica_apply_updates");
         buf_.clear();
         off_.assign(1, 0);
+    }
+};
+
+// HipDownstream for a caller that keeps its text as UTF-8 (EDITS_USE_BYTE_OFFSETS = true,
+// rope.rs:8,16-19, as the cola and yrs adapters): an Upstream too, whose insert, remove and replace
+// take byte offsets resolved on the device (crdt_hip_replica_replace_bytes); Patch::pos and
+// Patch::del of patches_since are bytes, and len() is a byte length.  crdt_bench does not run it
+// (its loop is the codepoint one); it is compiled with it.
+class HipDownstreamBytes : public HipDownstream {
+public:
+    static constexpr const char* NAME = "mi355x-device-bytes";
+    static constexpr bool EDITS_USE_BYTE_OFFSETS = true;
+
+    explicit HipDownstreamBytes(HipDownstream&& d) : HipDownstream(std::move(d)) {}
+    HipDownstreamBytes clone() const { return HipDownstreamBytes(HipDownstream::clone()); }
+    // Upstream::replace (rope.rs:21-32) in byte offsets; a boundary inside a codepoint is an error
+    void replace(size_t start, size_t end, std::string_view s) {
+        flush();
+        check(crdt_hip_replica_replace_bytes(dev_->ctx, rep_, start, end, s.data(), s.size()),
+              dev_->ctx, "replica_replace_bytes");
+    }
+    void insert(size_t at, std::string_view s) { replace(at, at, s); }
+    void remove(size_t start, size_t end) { replace(start, end, std::string_view()); }
+    // Upstream::len in bytes: the merged document's UTF-8 length (HipDownstream::len checks it
+    // against the decoder's counter).
+    size_t len() const {
+        (void)HipDownstream::len();
+        uint64_t items = 0, cps = 0, bytes = 0;
+        crdt_hip_replica_info(rep_, &items, &cps, &bytes);
+        return (size_t)bytes;
+    }
+    std::vector<Patch> patches_since(const Mark& m) const {
+        flush();
+        return patches_get(
+            [&](crdt_hip_patch* out, size_t cap, size_t* n, uint8_t* ins, size_t icap, size_t* nb) {
+                return crdt_hip_replica_patches_since_bytes(dev_->ctx, rep_, m.get(), out, cap, n,
+                                                            ins, icap, nb);
+            },
+            dev_->ctx, 4096, 1 << 16);
     }
 };
 

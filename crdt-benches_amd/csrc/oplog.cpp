@@ -799,6 +799,17 @@ LogMark OpLog::mark() const {
 
 int OpLog::patches_since(const LogMark& m, std::vector<PatchRec>& out, std::vector<uint8_t>& ins,
                          std::string& err) const {
+    return patches_walk(m, false, out, ins, err);
+}
+int OpLog::patches_since_bytes(const LogMark& m, std::vector<PatchRec>& out,
+                               std::vector<uint8_t>& ins, std::string& err) const {
+    return patches_walk(m, true, out, ins, err);
+}
+
+// The one walk behind both: an item weighs 1 (codepoints) or its UTF-8 length (bytes) in pos and
+// del; ins, ins_off and ins_len are bytes either way.
+int OpLog::patches_walk(const LogMark& m, bool bytes, std::vector<PatchRec>& out,
+                        std::vector<uint8_t>& ins, std::string& err) const {
     out.clear();
     ins.clear();
     if (size() < m.n || m.deleted.size() != m.n) {
@@ -808,28 +819,36 @@ int OpLog::patches_since(const LogMark& m, std::vector<PatchRec>& out, std::vect
     std::vector<uint32_t> order;
     err = document_order(order);
     if (!err.empty()) return CRDT_HIP_EBADLOG;
-    uint64_t pos = 0;   // `now` items so far
+    uint64_t pos = 0;   // `now` items (or their bytes) so far
+    uint64_t del = 0;   // what the open run deletes
     bool open = false;  // the previous K, D or I item was a D or an I: its run goes on
     for (uint32_t id : order) {
         const bool was = id <= m.n && !m.deleted[id - 1], now = !deleted[id - 1];
         if (!was && !now) continue;
+        const uint64_t w = bytes ? utf8_len_cp(cp[id - 1]) : 1;
         if (was && now) {
-            ++pos;
+            pos += w;
             open = false;
             continue;
         }
         if (!open) {
             out.push_back(PatchRec{pos, (uint64_t)ins.size(), 0u, 0u});
             open = true;
+            del = 0;
         }
         if (was) {
-            out.back().del++;
+            del += w;
+            if (del >= (1ull << 32)) {  // (bytes only: a log holds fewer than 2^31 items)
+                err = "a patch deletes 4 GiB or more";
+                return CRDT_HIP_ERANGE;
+            }
+            out.back().del = (uint32_t)del;
         } else {
             char b[4];
             const size_t k = utf8_put(cp[id - 1], b);
             ins.insert(ins.end(), b, b + k);
             out.back().ins_len += (uint32_t)k;
-            ++pos;
+            pos += bytes ? k : 1;
             if (ins.size() >= (1ull << 32)) {
                 err = "4 GiB or more of inserted bytes";
                 return CRDT_HIP_ERANGE;
@@ -840,19 +859,21 @@ int OpLog::patches_since(const LogMark& m, std::vector<PatchRec>& out, std::vect
 }
 
 // ---- local edits as positional patches ---------------------------------------------------------
-int edit_plan(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len, uint64_t visible,
-              uint64_t items, EditPlan& plan, std::string& err) {
-    plan.patch.clear();
-    plan.cps.clear();
-    plan.ndel = 0;
+// The argument-only checks of a patch array, in codepoints or (BYTES) in UTF-8 bytes: `visible`
+// and the non-touching rule are in the unit of pos and del.  emit(old position, del, first
+// codepoint, codepoints) per patch, the position in the document before the call.
+namespace {
+template <bool BYTES, class Emit>
+int plan_walk(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len, uint64_t visible,
+              uint64_t items, std::vector<uint32_t>& cps, std::string& err, Emit&& emit) {
+    cps.clear();
     if (n >= (1ull << 31)) {
         err = "2^31 or more patches";
         return CRDT_HIP_ERANGE;
     }
-    plan.patch.reserve(n);
     uint64_t len = visible;   // the document as the earlier patches left it
-    uint64_t next_min = 0;    // pos[k] must exceed pos[k - 1] + codepoints(ins[k - 1])
-    int64_t shift = 0;        // sum of (codepoints inserted - deleted) of the earlier patches
+    uint64_t next_min = 0;    // pos[k] must exceed pos[k - 1] + what patch k - 1 inserted
+    int64_t shift = 0;        // sum of (inserted - deleted) of the earlier patches
     for (size_t k = 0; k < n; ++k) {
         const PatchRec& r = p[k];
         if (r.del == 0 && r.ins_len == 0) {
@@ -863,12 +884,13 @@ int edit_plan(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len, u
             err = "patch text outside the ins buffer";
             return CRDT_HIP_EINVAL;
         }
-        const size_t c0 = plan.cps.size();
-        if (r.ins_len && !utf8_decode(reinterpret_cast<const char*>(ins) + r.ins_off, r.ins_len, plan.cps)) {
+        const size_t c0 = cps.size();
+        if (r.ins_len && !utf8_decode(reinterpret_cast<const char*>(ins) + r.ins_off, r.ins_len, cps)) {
             err = "invalid UTF-8";
             return CRDT_HIP_EINVAL;
         }
-        const uint64_t ncp = plan.cps.size() - c0;
+        const uint64_t ncp = cps.size() - c0;
+        const uint64_t added = BYTES ? (uint64_t)r.ins_len : ncp;
         if (k && r.pos < next_min) {
             err = "patches are not ascending and non-touching";
             return CRDT_HIP_EINVAL;
@@ -877,24 +899,85 @@ int edit_plan(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len, u
             err = "patch range beyond the document";
             return CRDT_HIP_ERANGE;
         }
-        if (items + plan.cps.size() >= 0x7FFFFFF0ull) {
+        if (items + cps.size() >= 0x7FFFFFF0ull) {
             err = "op log too large";
             return CRDT_HIP_ERANGE;
         }
-        EditPatch e;
-        e.old_pos = (uint32_t)((int64_t)r.pos - shift);
-        e.del = r.del;
-        e.cp0 = (uint32_t)c0;
-        e.ncp = (uint32_t)ncp;
-        e.del0 = (uint32_t)plan.ndel;
-        e.pad = 0;
-        plan.patch.push_back(e);
-        plan.ndel += r.del;
-        len = len - r.del + ncp;
-        shift += (int64_t)ncp - (int64_t)r.del;
-        next_min = r.pos + ncp + 1;
+        emit((uint64_t)((int64_t)r.pos - shift), r.del, (uint32_t)c0, (uint32_t)ncp);
+        len = len - r.del + added;
+        shift += (int64_t)added - (int64_t)r.del;
+        next_min = r.pos + added + 1;
     }
     return CRDT_HIP_OK;
+}
+}  // namespace
+
+int edit_plan(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len, uint64_t visible,
+              uint64_t items, EditPlan& plan, std::string& err) {
+    plan.patch.clear();
+    plan.ndel = 0;
+    if (n < (1ull << 31)) plan.patch.reserve(n);
+    return plan_walk<false>(p, n, ins, ins_len, visible, items, plan.cps, err,
+                            [&](uint64_t old_pos, uint32_t del, uint32_t c0, uint32_t ncp) {
+                                plan.patch.push_back(EditPatch{(uint32_t)old_pos, del, c0, ncp,
+                                                               (uint32_t)plan.ndel, 0u});
+                                plan.ndel += del;
+                            });
+}
+
+int edit_plan_bytes(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
+                    uint64_t visible_bytes, uint64_t items, EditPlanBytes& plan, std::string& err) {
+    plan.patch.clear();
+    if (n < (1ull << 31)) plan.patch.reserve(n);
+    return plan_walk<true>(p, n, ins, ins_len, visible_bytes, items, plan.cps, err,
+                           [&](uint64_t old_pos_b, uint32_t del_b, uint32_t c0, uint32_t ncp) {
+                               plan.patch.push_back(BytePatch{old_pos_b, del_b, c0, ncp});
+                           });
+}
+
+uint64_t OpLog::visible_bytes() const {
+    uint64_t b = 0;
+    for (uint32_t k = 0; k < size(); ++k)
+        if (!deleted[k]) b += utf8_len_cp(cp[k]);
+    return b;
+}
+
+int OpLog::apply_patches_bytes(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
+                               uint32_t* added, uint32_t* tombstoned, std::string& err) {
+    if (added) *added = 0;
+    if (tombstoned) *tombstoned = 0;
+    if (n == 0) return CRDT_HIP_OK;
+    EditPlanBytes plan;
+    const int rc = edit_plan_bytes(p, n, ins, ins_len, visible_bytes(), size(), plan, err);
+    if (rc) return rc;
+    std::vector<uint32_t> order;
+    err = document_order(order);
+    if (!err.empty()) return CRDT_HIP_EBADLOG;
+    // ends[v]: UTF-8 bytes of the first v visible items, the only byte offsets a patch may name
+    std::vector<uint64_t> ends;
+    ends.reserve((size_t)nvis_ + 1);
+    ends.push_back(0);
+    for (uint32_t id : order)
+        if (!deleted[id - 1]) ends.push_back(ends.back() + utf8_len_cp(cp[id - 1]));
+    auto rank_of = [&](uint64_t b, uint64_t& v) {
+        const auto it = std::lower_bound(ends.begin(), ends.end(), b);
+        if (it == ends.end() || *it != b) return false;
+        v = (uint64_t)(it - ends.begin());
+        return true;
+    };
+    std::vector<PatchRec> q(n);
+    int64_t shift = 0;  // codepoints inserted - deleted by the earlier patches
+    for (size_t k = 0; k < n; ++k) {
+        const BytePatch& e = plan.patch[k];
+        uint64_t v0, v1;
+        if (!rank_of(e.old_pos_b, v0) || !rank_of(e.old_pos_b + e.del_b, v1)) {
+            err = "patch boundary inside a codepoint";
+            return CRDT_HIP_EINVAL;
+        }
+        q[k] = PatchRec{(uint64_t)((int64_t)v0 + shift), p[k].ins_off, (uint32_t)(v1 - v0), p[k].ins_len};
+        shift += (int64_t)e.ncp - (int64_t)(v1 - v0);
+    }
+    return apply_patches(q.data(), n, ins, ins_len, added, tombstoned, err);
 }
 
 int OpLog::apply_patches(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,

@@ -114,6 +114,24 @@ struct EditPlan {
 // log), and fills the plan.  CRDT_HIP_OK, EINVAL or ERANGE with `err` set.
 int edit_plan(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len, uint64_t visible,
               uint64_t items, EditPlan& plan, std::string& err);
+// The byte-offset reading (crdt_hip.h, "byte offsets"; the device twin is bytes.hip): pos and del
+// count UTF-8 bytes of the visible document.  The same checks in the same order, in bytes, against
+// `visible_bytes`; what they cannot tell is whether a boundary falls inside a codepoint, which
+// needs the document.  Per patch its byte position in the document before the call,
+// old_pos_b = pos - sum over the earlier patches of (ins_len - del): the patches do not touch
+// there either, old_pos_b[k + 1] > old_pos_b[k] + del_b[k].
+struct BytePatch {
+    uint64_t old_pos_b;  // visible bytes before the patch in the document before the call
+    uint32_t del_b;      // bytes old_pos_b .. old_pos_b + del_b of that document are deleted
+    uint32_t cp0, ncp;   // as EditPatch
+    uint32_t pad = 0;
+};
+struct EditPlanBytes {
+    std::vector<BytePatch> patch;
+    std::vector<uint32_t> cps;
+};
+int edit_plan_bytes(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
+                    uint64_t visible_bytes, uint64_t items, EditPlanBytes& plan, std::string& err);
 
 class OpLog {
 public:
@@ -134,6 +152,7 @@ public:
     OpLog();
     uint32_t size() const { return (uint32_t)parent.size(); }
     uint64_t visible() const { return nvis_; }
+    uint64_t visible_bytes() const;  // UTF-8 bytes of the visible items (walks the columns)
 
     // Upstream::insert / remove (codepoint offsets).  Return "" or an error message.
     std::string insert(uint64_t pos, const uint32_t* cps, size_t k);
@@ -193,6 +212,10 @@ public:
     LogMark mark() const;
     int patches_since(const LogMark& m, std::vector<PatchRec>& out, std::vector<uint8_t>& ins,
                       std::string& err) const;
+    // The same runs with pos and del in UTF-8 bytes (crdt_hip.h, "byte offsets"); also ERANGE when
+    // one patch deletes 4 GiB or more.
+    int patches_since_bytes(const LogMark& m, std::vector<PatchRec>& out, std::vector<uint8_t>& ins,
+                            std::string& err) const;
     // Local edits as a set of positional patches in the patches_since convention (crdt_hip.h,
     // "local edits"): validated up front (edit_plan, then the lamport bound and the positional
     // index), and a rejected call changes nothing; then remove + insert per patch, in order, which
@@ -200,6 +223,12 @@ public:
     // *tombstoned: items deleted (either may be null).
     int apply_patches(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
                       uint32_t* added, uint32_t* tombstoned, std::string& err);
+    // The same with pos and del in UTF-8 bytes: edit_plan_bytes, then every boundary is translated
+    // to a codepoint rank through the visible byte ends of document_order (a boundary inside a
+    // codepoint: EINVAL) and the translated array goes to apply_patches.  The definition the device
+    // path is held to, not a product path: a call walks the whole document.
+    int apply_patches_bytes(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
+                            uint32_t* added, uint32_t* tombstoned, std::string& err);
     // Every item id in document order, tombstones included (RGA pre-order or Fugue in-order): the
     // sibling sort and walk that rebuild_index / rebuild_index_fugue build their index from.
     std::string document_order(std::vector<uint32_t>& order) const;
@@ -215,6 +244,8 @@ public:
     void reserve(size_t items, size_t dels = 0);
 
 private:
+    int patches_walk(const LogMark& m, bool bytes, std::vector<PatchRec>& out,
+                     std::vector<uint8_t>& ins, std::string& err) const;
     // RGA positional index: the visible items in document order as a gap buffer of spans (runs
     // of consecutive ids; typing extends the span before the gap), the gap at the last edit and
     // the visible items before it (gvis_), so an edit next to the previous one moves nothing and a

@@ -39,10 +39,16 @@
 // No atomic decides an order; every index is checked against n, n_mark and the output sizes
 // before use; the patch array and the text are copied out in one transfer each.
 //
+// The byte-offset reading (crdt_hip_replica_patches_since_bytes; crdt_hip.h, "byte offsets") is the
+// BYTES instantiation of the same kernels: an item weighs its UTF-8 length instead of 1 in the
+// `now` and D sums, the prefixes over the tiles are 64-bit, and k_patch_finish refuses a patch
+// that deletes 4 GiB or more instead of truncating its del.
+//
 // Known cost: a call streams every rank of the replica however small the change, and after a join
 // or a delta it also pays inc_rebuild's ORDER-mode merge with its host round trip for the order.
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "idtab.hpp"
@@ -60,18 +66,35 @@ constexpr uint32_t C_NONE = 0, C_K = 1, C_D = 2, C_I = 3;
 
 // device counters (u64)
 enum PCtl { P_ERR = 0, P_PATCHES, P_IBYTES, P_NOW, P_DEL, P_N };
-constexpr uint64_t EP_SLOT = 1;  // the order names a slot that is no item of the replica
+constexpr uint64_t EP_SLOT = 1;   // the order names a slot that is no item of the replica
+constexpr uint64_t EP_RANGE = 2;  // (bytes) one patch deletes 4 GiB or more
+
+// BYTES: pos and del count UTF-8 bytes instead of items (crdt_hip.h, "byte offsets").  A compile-
+// time parameter of every kernel below: the codepoint instantiation weighs an item as the constant
+// 1 and keeps 32-bit prefixes.  A tile of 4,096 ranks holds at most 16 KiB, so the sums inside a
+// tile fit 32 bits either way; the prefixes over the tiles do not in bytes (a replica may hold more
+// than 2^32 visible bytes) and are 64-bit there.
+template <bool BYTES>
+using PosW = typename std::conditional<BYTES, uint64_t, uint32_t>::type;
+template <bool BYTES>
+__device__ __forceinline__ uint32_t item_w(uint32_t cpw) {
+    if constexpr (BYTES) return utf8_len(cpw);
+    else return 1u;
+}
 
 struct TileAgg {
     uint32_t now, del, ibytes, heads;  // counts inside the tile (heads: the decided ones)
     uint32_t first, last;              // class of the tile's first / last K, D or I item
 };
+template <bool BYTES>
 struct TilePre {
     uint64_t ibytes;                   // exclusive prefixes over the tiles before this one
-    uint32_t now, del, heads;
+    PosW<BYTES> now, del;
+    uint32_t heads;
     uint32_t carry;                    // class of the last K, D or I item before the tile
 };
 
+template <bool BYTES>
 struct PatchArgs {
     const uint32_t* seq;   // rank -> slot, ranks 0..n (rank 0 = slot 0, the document start)
     const uint8_t* cp;     // 3-byte codepoint words of slots 0..n
@@ -80,12 +103,12 @@ struct PatchArgs {
     uint64_t mark_words;
     uint32_t ntiles;
     TileAgg* agg;
-    TilePre* pre;
+    TilePre<BYTES>* pre;
     // write pass (sizes as the host read them)
     uint32_t npatch;
     uint64_t nibytes;
-    uint64_t* hpos;        // per head: `now` items, D items, I bytes before it
-    uint32_t* hdel;
+    uint64_t* hpos;        // per head: `now` items, D items (or their bytes), I bytes before it
+    PosW<BYTES>* hdel;
     uint64_t* hib;
     PatchRec* out;
     uint8_t* ins;
@@ -110,7 +133,8 @@ __global__ __launch_bounds__(kJB) void k_mark_pack(const uint8_t* cp, uint32_t n
 // ---- classify ----------------------------------------------------------------------------------
 // The classes and codepoints of the thread's four ranks k0..k0 + 3 (ranks past n, rank 0 and
 // slots that are no item: C_NONE).
-__device__ __forceinline__ void patch_load(const PatchArgs& a, uint64_t k0, uint32_t cls[kOrdPer],
+template <bool BYTES>
+__device__ __forceinline__ void patch_load(const PatchArgs<BYTES>& a, uint64_t k0, uint32_t cls[kOrdPer],
                                            uint32_t cpw[kOrdPer], uint64_t& err) {
 #pragma unroll
     for (uint32_t j = 0; j < kOrdPer; ++j) {
@@ -132,6 +156,7 @@ __device__ __forceinline__ void patch_load(const PatchArgs& a, uint64_t k0, uint
 struct ThreadSum {
     uint32_t now, del, ibytes, heads, first, last;
 };
+template <bool BYTES>
 __device__ __forceinline__ ThreadSum patch_sum(const uint32_t cls[kOrdPer],
                                                const uint32_t cpw[kOrdPer]) {
     ThreadSum t{0, 0, 0, 0, C_NONE, C_NONE};
@@ -139,8 +164,8 @@ __device__ __forceinline__ ThreadSum patch_sum(const uint32_t cls[kOrdPer],
     for (uint32_t j = 0; j < kOrdPer; ++j) {
         const uint32_t c = cls[j];
         if (c == C_NONE) continue;
-        if (c != C_D) t.now++;
-        if (c == C_D) t.del++;
+        if (c != C_D) t.now += item_w<BYTES>(cpw[j]);
+        if (c == C_D) t.del += item_w<BYTES>(cpw[j]);
         if (c == C_I) t.ibytes += utf8_len(cpw[j]);
         if (t.last == C_NONE) t.first = c;
         else if (c != C_K && t.last == C_K) t.heads++;
@@ -172,7 +197,8 @@ __device__ __forceinline__ uint32_t patch_incoming(uint32_t last, uint32_t* wlas
     return below ? inwave : carry;
 }
 
-__global__ __launch_bounds__(kOrdT) void k_patch_classify(PatchArgs a) {
+template <bool BYTES>
+__global__ __launch_bounds__(kOrdT) void k_patch_classify(PatchArgs<BYTES> a) {
     __shared__ uint32_t red[kOrdW];
     __shared__ uint32_t wfirst[kOrdW];
     const uint64_t k0 = (uint64_t)blockIdx.x * kOrderTile + (uint64_t)threadIdx.x * kOrdPer;
@@ -180,7 +206,7 @@ __global__ __launch_bounds__(kOrdT) void k_patch_classify(PatchArgs a) {
     uint64_t err = 0;
     patch_load(a, k0, cls, cpw, err);
     ctl_or(&a.ctl[P_ERR], err);
-    const ThreadSum t = patch_sum(cls, cpw);
+    const ThreadSum t = patch_sum<BYTES>(cls, cpw);
     const uint32_t inc = patch_incoming(t.last, red);
     // the thread's first item: a head iff it is a D or an I behind a K (behind nothing: the
     // tile's first item, left to k_patch_top)
@@ -239,7 +265,8 @@ __device__ __forceinline__ uint32_t block_excl_max(uint32_t x, uint32_t* lds, ui
     return lane ? max(off, prev) : off;
 }
 
-__global__ __launch_bounds__(kOrdTop) void k_patch_top(PatchArgs a) {
+template <bool BYTES>
+__global__ __launch_bounds__(kOrdTop) void k_patch_top(PatchArgs<BYTES> a) {
     __shared__ uint32_t lds[kOrdTop / 64];
     uint64_t c_now = 0, c_del = 0, c_ib = 0, c_heads = 0;
     uint32_t c_last = 0;  // (tile index + 1) << 2 | class of the last tile so far that holds an item
@@ -252,11 +279,11 @@ __global__ __launch_bounds__(kOrdTop) void k_patch_top(PatchArgs a) {
         c_last = max(c_last, tot);
         const uint32_t carry = seen & 3u;  // (C_NONE: the start of the document)
         const uint32_t heads = g.heads + (g.first >= C_D && (carry == C_K || carry == C_NONE) ? 1u : 0u);
-        TilePre p;
+        TilePre<BYTES> p;
         p.carry = carry;
-        p.now = (uint32_t)c_now + block_excl_scan<kOrdTop / 64>(g.now, lds, tot);
+        p.now = (PosW<BYTES>)c_now + block_excl_scan<kOrdTop / 64>(g.now, lds, tot);
         c_now += tot;
-        p.del = (uint32_t)c_del + block_excl_scan<kOrdTop / 64>(g.del, lds, tot);
+        p.del = (PosW<BYTES>)c_del + block_excl_scan<kOrdTop / 64>(g.del, lds, tot);
         c_del += tot;
         p.ibytes = c_ib + block_excl_scan<kOrdTop / 64>(g.ibytes, lds, tot);
         c_ib += tot;
@@ -273,15 +300,16 @@ __global__ __launch_bounds__(kOrdTop) void k_patch_top(PatchArgs a) {
 }
 
 // ---- write -------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kOrdT) void k_patch_write(PatchArgs a) {
+template <bool BYTES>
+__global__ __launch_bounds__(kOrdT) void k_patch_write(PatchArgs<BYTES> a) {
     __shared__ uint32_t lds[kOrdW];
     if (blockIdx.x >= a.ntiles) return;
     const uint64_t k0 = (uint64_t)blockIdx.x * kOrderTile + (uint64_t)threadIdx.x * kOrdPer;
     uint32_t cls[kOrdPer], cpw[kOrdPer];
     uint64_t err = 0;
     patch_load(a, k0, cls, cpw, err);  // (k_patch_classify reported any error)
-    const ThreadSum t = patch_sum(cls, cpw);
-    const TilePre p = a.pre[blockIdx.x];
+    const ThreadSum t = patch_sum<BYTES>(cls, cpw);
+    const TilePre<BYTES> p = a.pre[blockIdx.x];
     uint32_t inc = patch_incoming(t.last, lds);
     // nothing before the thread in its tile: what the tiles before carry (the start of the
     // document opens a run like a K does)
@@ -289,7 +317,7 @@ __global__ __launch_bounds__(kOrdT) void k_patch_write(PatchArgs a) {
     const uint32_t heads = t.heads + (t.first >= C_D && inc == C_K ? 1u : 0u);
     uint32_t tot;
     uint64_t now = (uint64_t)p.now + block_excl_scan<kOrdW>(t.now, lds, tot);
-    uint32_t del = p.del + block_excl_scan<kOrdW>(t.del, lds, tot);
+    PosW<BYTES> del = p.del + block_excl_scan<kOrdW>(t.del, lds, tot);
     uint64_t ib = p.ibytes + block_excl_scan<kOrdW>(t.ibytes, lds, tot);
     uint32_t h = p.heads + block_excl_scan<kOrdW>(heads, lds, tot);
     uint32_t prev = inc;
@@ -327,22 +355,29 @@ __global__ __launch_bounds__(kOrdT) void k_patch_write(PatchArgs a) {
             }
             ib += len;
         }
-        if (c == C_D) ++del;
-        else ++now;
+        if (c == C_D) del += item_w<BYTES>(cpw[j]);
+        else now += item_w<BYTES>(cpw[j]);
         prev = c;
     }
 }
 
-__global__ __launch_bounds__(kJB) void k_patch_finish(PatchArgs a, uint32_t total_del) {
+template <bool BYTES>
+__global__ __launch_bounds__(kJB) void k_patch_finish(PatchArgs<BYTES> a, PosW<BYTES> total_del) {
     const uint32_t h = blockIdx.x * kJB + threadIdx.x;
     if (h >= a.npatch) return;
     const bool lastp = h + 1u == a.npatch;
-    const uint32_t d1 = lastp ? total_del : a.hdel[h + 1u];
+    const PosW<BYTES> d1 = lastp ? total_del : a.hdel[h + 1u];
     const uint64_t b1 = lastp ? a.nibytes : a.hib[h + 1u];
     PatchRec r;
     r.pos = a.hpos[h];
     r.ins_off = a.hib[h];
-    r.del = d1 - a.hdel[h];
+    r.del = (uint32_t)(d1 - a.hdel[h]);
+    if constexpr (BYTES) {  // del is a uint32_t: 4 GiB or more is an error, never a truncation
+        if (d1 - a.hdel[h] >= (1ull << 32)) {
+            ctl_or(&a.ctl[P_ERR], EP_RANGE);
+            r.del = 0xFFFFFFFFu;
+        }
+    }
     r.ins_len = (uint32_t)(b1 - a.hib[h]);
     a.out[h] = r;
 }
@@ -382,9 +417,11 @@ int replica_mark(Engine& E, Replica& r, DeviceMark& m) {
     return CRDT_HIP_OK;
 }
 
-int replica_patches_since(Engine& E, Replica& r, const DeviceMark& m, PatchRec* out, size_t cap,
-                          size_t* out_n, uint8_t* ins, size_t ins_cap, size_t* out_ins,
-                          PatchStats* stats) {
+namespace {
+template <bool BYTES>
+int patches_since_impl(Engine& E, Replica& r, const DeviceMark& m, PatchRec* out, size_t cap,
+                       size_t* out_n, uint8_t* ins, size_t ins_cap, size_t* out_ins,
+                       PatchStats* stats) {
     if (stats) *stats = PatchStats{};
     *out_n = 0;
     *out_ins = 0;
@@ -396,7 +433,7 @@ int replica_patches_since(Engine& E, Replica& r, const DeviceMark& m, PatchRec* 
         return CRDT_HIP_EINVAL;
     }
     if (r.n == 0) return CRDT_HIP_OK;  // nothing held: nothing changed
-    PatchArgs a{};
+    PatchArgs<BYTES> a{};
     rc = replica_kept_order(E, r, "patches", &a.seq, &a.ntiles);
     if (rc) return rc;
     hipStream_t s = E.stream;
@@ -412,8 +449,8 @@ int replica_patches_since(Engine& E, Replica& r, const DeviceMark& m, PatchRec* 
     a.ctl = sc.ctl;
     HIPTRY(E, sc.time_begin(), "patch event");
     k_patch_init<<<1, 64, 0, s>>>(sc.ctl);
-    k_patch_classify<<<a.ntiles, kOrdT, 0, s>>>(a);
-    k_patch_top<<<1, kOrdTop, 0, s>>>(a);
+    k_patch_classify<BYTES><<<a.ntiles, kOrdT, 0, s>>>(a);
+    k_patch_top<BYTES><<<1, kOrdTop, 0, s>>>(a);
     HIPTRY(E, hipGetLastError(), "patch classify kernels");
     HIPTRY(E, sc.time_end(), "patch event");
     HIPTRY(E, hipMemcpyAsync(sc.hctl, sc.ctl, P_N * 8, hipMemcpyDeviceToHost, s), "copy patch counters");
@@ -423,7 +460,7 @@ int replica_patches_since(Engine& E, Replica& r, const DeviceMark& m, PatchRec* 
         E.err = "patches: the kept document order names a slot that is no item";
         return CRDT_HIP_EBADLOG;
     }
-    if (sc.hctl[P_NOW] != r.vis_cp) {
+    if (sc.hctl[P_NOW] != (BYTES ? r.vis_bytes : r.vis_cp)) {
         E.err = "patches: the visible items of the kept order disagree with the replica's counter";
         return CRDT_HIP_EBADLOG;
     }
@@ -453,16 +490,34 @@ int replica_patches_since(Engine& E, Replica& r, const DeviceMark& m, PatchRec* 
     HIPTRY(E, sc.alloc(&a.out, np), "hipMalloc patches");
     HIPTRY(E, sc.alloc(&a.ins, nib), "hipMalloc patch text");
     HIPTRY(E, sc.time_begin(), "patch event");
-    k_patch_write<<<a.ntiles, kOrdT, 0, s>>>(a);
-    k_patch_finish<<<grid_for(np, kJB), kJB, 0, s>>>(a, (uint32_t)sc.hctl[P_DEL]);
+    k_patch_write<BYTES><<<a.ntiles, kOrdT, 0, s>>>(a);
+    k_patch_finish<BYTES><<<grid_for(np, kJB), kJB, 0, s>>>(a, (PosW<BYTES>)sc.hctl[P_DEL]);
     HIPTRY(E, hipGetLastError(), "patch write kernels");
     HIPTRY(E, sc.time_end(), "patch event");
     HIPTRY(E, hipMemcpyAsync(out, a.out, np * sizeof(PatchRec), hipMemcpyDeviceToHost, s), "copy patches");
     if (nib) HIPTRY(E, hipMemcpyAsync(ins, a.ins, nib, hipMemcpyDeviceToHost, s), "copy patch text");
+    if (BYTES)  // (k_patch_finish may have raised EP_RANGE: the same wait brings it back)
+        HIPTRY(E, hipMemcpyAsync(sc.hctl, sc.ctl, 8, hipMemcpyDeviceToHost, s), "copy patch counters");
     HIPTRY(E, hipStreamSynchronize(s), "patch sync");
     sc.time_add();
     if (stats) stats->device_ns = sc.dev_ns;
+    if (BYTES && sc.hctl[P_ERR]) {
+        E.err = "patches: a patch deletes 4 GiB or more";
+        return CRDT_HIP_ERANGE;
+    }
     return CRDT_HIP_OK;
+}
+}  // namespace
+
+int replica_patches_since(Engine& E, Replica& r, const DeviceMark& m, PatchRec* out, size_t cap,
+                          size_t* out_n, uint8_t* ins, size_t ins_cap, size_t* out_ins,
+                          PatchStats* stats) {
+    return patches_since_impl<false>(E, r, m, out, cap, out_n, ins, ins_cap, out_ins, stats);
+}
+int replica_patches_since_bytes(Engine& E, Replica& r, const DeviceMark& m, PatchRec* out,
+                                size_t cap, size_t* out_n, uint8_t* ins, size_t ins_cap,
+                                size_t* out_ins, PatchStats* stats) {
+    return patches_since_impl<true>(E, r, m, out, cap, out_n, ins, ins_cap, out_ins, stats);
 }
 
 }  // namespace crdt

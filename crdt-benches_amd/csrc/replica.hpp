@@ -249,6 +249,18 @@ struct EditStats {  // what the last device apply_patches observed (crdt_hip_edi
 int replica_apply_patches(Engine& E, Replica& r, const PatchRec* p, size_t n, const uint8_t* ins,
                           size_t ins_len, uint32_t* added, uint32_t* tombstoned,
                           EditStats* stats = nullptr);
+// The byte-offset reading of both (crdt_hip.h, "byte offsets"): pos and del count UTF-8 bytes of
+// the visible document.  patches_since_bytes is the BYTES instantiation of patch.hip's kernels
+// (64-bit prefixes over the tiles; ERANGE also when one patch deletes 4 GiB or more).
+// apply_patches_bytes translates the boundaries to codepoint ranks in the kernels of bytes.hip (a
+// boundary inside a codepoint: EINVAL, after every other check but the lamport bound), then runs
+// the resolve, emit and decode of edit.hip unchanged; it waits for the host twice before the decode.
+int replica_patches_since_bytes(Engine& E, Replica& r, const DeviceMark& m, PatchRec* out,
+                                size_t cap, size_t* out_n, uint8_t* ins, size_t ins_cap,
+                                size_t* out_ins, PatchStats* stats = nullptr);
+int replica_apply_patches_bytes(Engine& E, Replica& r, const PatchRec* p, size_t n,
+                                const uint8_t* ins, size_t ins_len, uint32_t* added,
+                                uint32_t* tombstoned, EditStats* stats = nullptr);
 
 // The document order of every item r holds, as a merge_inc leaves it (and leaving r as a merge_inc
 // does): *seq = rank -> slot for ranks 0..n, *ntiles = its tiles of kOrderTile ranks (order.hpp).

@@ -32,13 +32,17 @@
  *   insert / remove / replace on the device (Upstream for a resident replica)
  *                        -> crdt_hip_replica_replace / crdt_hip_replica_apply_patches ("local
  *                           edits"): positions resolved to identities in HIP kernels
+ *   EDITS_USE_BYTE_OFFSETS = true (rope.rs:8,16-19; the cola and yrs adapters)
+ *                        -> the *_bytes twins of replace, apply_patches and patches_since, on the
+ *                           host and on the device ("byte offsets"): positions in UTF-8 bytes
  *
  * Conventions
  *   - Every function returns int status: 0 = ok, < 0 = error (CRDT_HIP_E*).  Nothing throws or
  *     aborts across the ABI.  crdt_hip_last_error(ctx) returns the message of the last failure
  *     on that context (ctx == NULL: the last failure of a context-free call on this thread).
  *   - Host pointers are BORROWED for the duration of the call only.
- *   - Positions are Unicode codepoints (EDITS_USE_BYTE_OFFSETS = false, rope.rs:8,16-19).
+ *   - Positions are Unicode codepoints (EDITS_USE_BYTE_OFFSETS = false, rope.rs:8,16-19), except
+ *     in the functions named *_bytes ("byte offsets"), which take and report UTF-8 bytes.
  *   - A context is bound to one HIP device and must be used by one host thread at a time; calls
  *     are synchronous at the ABI (the work runs on the context's own HIP stream).
  *   - Op log ids: items are 1..n in creation order; id 0 is the document start (origin of an
@@ -426,6 +430,77 @@ int crdt_hip_replica_replace(crdt_hip_ctx* ctx, crdt_hip_replica* r, size_t star
  * update they write included (HIP events; the order update is not included). */
 int crdt_hip_edit_stats(const crdt_hip_ctx* ctx, uint64_t* patches, uint64_t* items,
                         uint64_t* tombstones, uint64_t* ranks, uint64_t* device_ns);
+
+/* ---- byte offsets: the same patches with pos and del in UTF-8 bytes ----------------------------
+ * For a caller that keeps its text as UTF-8 (EDITS_USE_BYTE_OFFSETS = true, rope.rs:8,16-19: the
+ * cola and yrs adapters; a Rust String, a rope of bytes): the *_bytes twins of the two sections
+ * above take and report positions in UTF-8 bytes of the visible document, so no text is kept
+ * beside the log or the replica to translate them.  The same crdt_hip_patch struct: pos and del are
+ * bytes, ins_off and ins_len were bytes already.  Every codepoint function and its results are
+ * unchanged.  crdt_hip_oplog_visible_bytes: the visible UTF-8 bytes of a log (walks the columns;
+ * a replica reports them in crdt_hip_replica_info).
+ *
+ * Local edits, *_apply_patches_bytes.  The array reads in the patches_since convention, in bytes:
+ * patch k is replace(pos..pos + del, ins[ins_off, +ins_len)), pos counted in the document as the
+ * earlier patches of the array left it.  The result is defined through the codepoint call:
+ * translate every patch through the text of the document before the call (codepoint pos = the
+ * codepoints in its first pos bytes, codepoint del = the codepoints in the del bytes that follow);
+ * the log is then, slot for slot, the log crdt_hip_oplog_apply_patches gives for the translated
+ * array.  *added and *tombstoned stay item counts.  Everything is validated before anything
+ * changes, and a rejected call changes nothing; n == 0 is ok and changes nothing.  The checks run
+ * in array order and, within a patch, in this order:
+ *   CRDT_HIP_EINVAL  del == 0 and ins_len == 0
+ *   CRDT_HIP_EINVAL  a piece [ins_off, ins_off + ins_len) outside `ins`
+ *   CRDT_HIP_EINVAL  a piece that is not UTF-8 by the rule of crdt_hip_oplog_insert
+ *   CRDT_HIP_EINVAL  unless pos[k + 1] > pos[k] + ins_len[k]
+ *   CRDT_HIP_ERANGE  pos + del beyond the visible bytes, as the earlier patches left them
+ *   CRDT_HIP_ERANGE  an item count that would reach the op-log limit
+ * then, only when every patch passed them,
+ *   CRDT_HIP_EINVAL  a pos or a pos + del that falls inside a codepoint of the document (Rust's
+ *                    String::replace_range panics on the same condition)
+ * and after that
+ *   CRDT_HIP_ERANGE  lamports that would reach 0xFFFFFFFF
+ * *_replace_bytes is one patch with Upstream::replace's reading (rope.rs:21-32): remove if
+ * end > start, insert if nbytes > 0, nothing otherwise.
+ *
+ * Patches since a mark, *_patches_since_bytes.  The same runs of D and I items as patches_since:
+ * pos = the UTF-8 bytes of the `now` items before the run, del = the UTF-8 bytes of the run's D
+ * items; ins, ins_off and ins_len are unchanged.  Applied in order to the UTF-8 of the document at
+ * the mark, each as a splice of bytes, the patches give the UTF-8 of the current document, and
+ * they never touch: pos[k + 1] > pos[k] + ins_len[k].  CRDT_HIP_ERANGE also when one patch deletes
+ * 4 GiB or more (del is a uint32_t and is never truncated).  Everything else is as for
+ * patches_since: the mark's owner and lifetime, the ESPACE sizing, and a device call leaves the
+ * replica as a merge_inc would.  Host and device return the same array and the same bytes.
+ *
+ * The host calls are the definition, not a product path: crdt_hip_oplog_apply_patches_bytes takes
+ * the document order from the log itself and builds a table of visible byte ends per call, so a
+ * call costs O(items) and a keystroke loop O(n^2).  The device calls are the product: patches_since
+ * in bytes is the same classification, scan and compaction with UTF-8 lengths as weights (64-bit
+ * prefixes over the tiles); apply_patches in bytes adds one streaming pass over the kept order that
+ * gives every visible item its byte end, lets it find the patch boundary it is, and builds the
+ * codepoint patch table on the device, then resolves, emits and decodes exactly as the codepoint
+ * call does.  It waits for the host twice before the decode (the boundary check and the number of
+ * deleted items, then the codepoint call's own wait).  crdt_hip_edit_stats and
+ * crdt_hip_patch_stats report the byte calls too (the translation kernels included).
+ * crdt_hip_trace_resolve keeps refusing a trace that went through chars_to_bytes. */
+int crdt_hip_oplog_visible_bytes(const crdt_hip_oplog* log, uint64_t* out);
+int crdt_hip_oplog_apply_patches_bytes(crdt_hip_oplog* log, const crdt_hip_patch* p, size_t n,
+                                       const uint8_t* ins, size_t ins_len, uint32_t* added,
+                                       uint32_t* tombstoned);
+int crdt_hip_oplog_replace_bytes(crdt_hip_oplog* log, size_t start, size_t end, const char* utf8,
+                                 size_t nbytes);
+int crdt_hip_oplog_patches_since_bytes(crdt_hip_oplog* log, const crdt_hip_mark* m,
+                                       crdt_hip_patch* out, size_t cap, size_t* out_n, uint8_t* ins,
+                                       size_t ins_cap, size_t* out_ins);
+int crdt_hip_replica_apply_patches_bytes(crdt_hip_ctx* ctx, crdt_hip_replica* r,
+                                         const crdt_hip_patch* p, size_t n, const uint8_t* ins,
+                                         size_t ins_len, uint32_t* added, uint32_t* tombstoned);
+int crdt_hip_replica_replace_bytes(crdt_hip_ctx* ctx, crdt_hip_replica* r, size_t start, size_t end,
+                                   const char* utf8, size_t nbytes);
+int crdt_hip_replica_patches_since_bytes(crdt_hip_ctx* ctx, crdt_hip_replica* r,
+                                         const crdt_hip_mark* m, crdt_hip_patch* out, size_t cap,
+                                         size_t* out_n, uint8_t* ins, size_t ins_cap,
+                                         size_t* out_ins);
 
 /* ---- trace loader (crdt-testdata load_testing_data / chars_to_bytes, main.rs:19-23) ---------- */
 int crdt_hip_trace_load(const char* path, crdt_hip_trace** out);
