@@ -63,6 +63,10 @@ EXPORTS = [
     "crdt_hip_replica_mark", "crdt_hip_replica_patches_since", "crdt_hip_patch_stats",
     "crdt_hip_oplog_apply_patches", "crdt_hip_replica_set_agent",
     "crdt_hip_replica_apply_patches", "crdt_hip_replica_replace", "crdt_hip_edit_stats",
+    "crdt_hip_oplog_anchors_at", "crdt_hip_oplog_anchors_at_bytes",
+    "crdt_hip_oplog_anchors_resolve", "crdt_hip_replica_anchors_at",
+    "crdt_hip_replica_anchors_at_bytes", "crdt_hip_replica_anchors_resolve",
+    "crdt_hip_anchor_stats",
 ]
 
 
@@ -205,6 +209,13 @@ def lib() -> C.CDLL:
         "crdt_hip_replica_apply_patches_bytes": (i32, [vp, vp, vp, sz, vp, sz, P(u32), P(u32)]),
         "crdt_hip_replica_replace_bytes": (i32, [vp, vp, sz, sz, C.c_char_p, sz]),
         "crdt_hip_replica_patches_since_bytes": (i32, [vp, vp, vp, vp, sz, P(sz), vp, sz, P(sz)]),
+        "crdt_hip_oplog_anchors_at": (i32, [vp, vp, vp, sz, vp]),
+        "crdt_hip_oplog_anchors_at_bytes": (i32, [vp, vp, vp, sz, vp]),
+        "crdt_hip_oplog_anchors_resolve": (i32, [vp, vp, sz, vp]),
+        "crdt_hip_replica_anchors_at": (i32, [vp, vp, vp, vp, sz, vp]),
+        "crdt_hip_replica_anchors_at_bytes": (i32, [vp, vp, vp, vp, sz, vp]),
+        "crdt_hip_replica_anchors_resolve": (i32, [vp, vp, vp, sz, vp]),
+        "crdt_hip_anchor_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge": (i32, [vp, vp, vp, sz, P(sz), P(u64)]),
         "crdt_hip_replica_merge_len": (i32, [vp, vp, P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge_inc": (i32, [vp, vp, vp, sz, P(sz), P(u64), P(u32)]),
@@ -408,6 +419,73 @@ def _patches_pack(patches, ins=None) -> tuple:
     return arr, b"".join(parts)
 
 
+# Anchors (crdt_hip.h, "anchors"): a place in the text named by the identity of the item next to
+# the gap, with a bias.
+AFTER, BEFORE = 0, 1
+LIVE, DEAD, UNKNOWN = 0, 1, 2
+EDGE = 0xFFFFFFFFFFFFFFFF
+
+
+class Anchor(C.Structure):
+    """crdt_hip_anchor: 16 plain bytes, shipped to another peer as they are."""
+    _fields_ = [("id", C.c_uint64), ("bias", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class AnchorPos(C.Structure):
+    """crdt_hip_anchor_pos: where an anchor lies in the visible document now."""
+    _fields_ = [("pos", C.c_uint64), ("pos_bytes", C.c_uint64), ("state", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+ANCHOR_DTYPE = np.dtype([("id", "<u8"), ("bias", "<u4"), ("pad", "<u4")])
+ANCHOR_POS_DTYPE = np.dtype([("pos", "<u8"), ("pos_bytes", "<u8"), ("state", "<u4"), ("pad", "<u4")])
+assert ANCHOR_DTYPE.itemsize == C.sizeof(Anchor) == 16
+assert ANCHOR_POS_DTYPE.itemsize == C.sizeof(AnchorPos) == 24
+
+
+def _anchors_at(call, positions, bias, ctx=None, out=None) -> np.ndarray:
+    """call(pos, bias, n, out) -> the crdt_hip_anchor array.  `bias`: a scalar or one per
+    position.  `out`: an array to write into (a failed call leaves it untouched)."""
+    pos = np.ascontiguousarray(positions, dtype=np.uint64).reshape(-1)
+    b = np.ascontiguousarray(np.broadcast_to(np.asarray(bias, dtype=np.uint8), pos.shape))
+    if out is None:
+        out = np.zeros(pos.size, ANCHOR_DTYPE)
+    assert out.dtype == ANCHOR_DTYPE and out.size == pos.size
+    _check(call(pos.ctypes.data if pos.size else None, b.ctypes.data if b.size else None, pos.size,
+                out.ctypes.data if out.size else None), ctx)
+    return out
+
+
+def _anchors_pack(anchors) -> np.ndarray:
+    """[(id, bias)] or a structured array of ANCHOR_DTYPE (passed through unchecked)."""
+    if isinstance(anchors, np.ndarray) and anchors.dtype == ANCHOR_DTYPE:
+        return np.ascontiguousarray(anchors)
+    alist = list(anchors)
+    arr = np.zeros(len(alist), ANCHOR_DTYPE)
+    for k, (ident, bias) in enumerate(alist):
+        arr[k] = (ident, bias, 0)
+    return arr
+
+
+def _anchors_resolve(call, anchors, ctx=None, out=None) -> np.ndarray:
+    """call(anchors, n, out) -> the crdt_hip_anchor_pos array."""
+    arr = _anchors_pack(anchors)
+    if out is None:
+        out = np.zeros(arr.size, ANCHOR_POS_DTYPE)
+    assert out.dtype == ANCHOR_POS_DTYPE and out.size == arr.size
+    _check(call(arr.ctypes.data if arr.size else None, arr.size,
+                out.ctypes.data if out.size else None), ctx)
+    return out
+
+
+def _anchor_list(raw: np.ndarray) -> list:
+    return [(int(a["id"]), int(a["bias"])) for a in raw]
+
+
+def _anchor_pos_list(raw: np.ndarray) -> list:
+    return [(int(p["pos"]), int(p["pos_bytes"]), int(p["state"])) for p in raw]
+
+
 class OpLog:
     """Host-side resolver (positional patches -> anchor op log), crdt_hip_oplog_*."""
 
@@ -588,6 +666,36 @@ class OpLog:
         """patches_since with pos and del in UTF-8 bytes: spliced in order into the UTF-8 of the
         text at the mark they give the UTF-8 now (crdt_hip_oplog_patches_since_bytes)."""
         return _patch_list(self.patches_since_bytes_raw(mark))
+
+    # Anchors (crdt_hip.h, "anchors").  The host calls are the definition the device calls are held
+    # to; a call walks the whole document.
+    def anchors_at_raw(self, positions, bias=AFTER, out=None) -> np.ndarray:
+        return _anchors_at(lambda *a: lib().crdt_hip_oplog_anchors_at(self._h, *a), positions, bias,
+                           out=out)
+
+    def anchors_at_bytes_raw(self, positions, bias=AFTER, out=None) -> np.ndarray:
+        return _anchors_at(lambda *a: lib().crdt_hip_oplog_anchors_at_bytes(self._h, *a), positions,
+                           bias, out=out)
+
+    def resolve_anchors_raw(self, anchors, out=None) -> np.ndarray:
+        return _anchors_resolve(lambda *a: lib().crdt_hip_oplog_anchors_resolve(self._h, *a),
+                                anchors, out=out)
+
+    def anchors_at(self, positions, bias=AFTER) -> list:
+        """Gap positions 0..len of the visible document (codepoints) -> [(id, bias)]: AFTER names
+        the item before the gap, BEFORE the one after it, EDGE the document's start or end
+        (crdt_hip_oplog_anchors_at).  `bias`: a scalar or one per position."""
+        return _anchor_list(self.anchors_at_raw(positions, bias))
+
+    def anchors_at_bytes(self, positions, bias=AFTER) -> list:
+        """anchors_at with positions in UTF-8 bytes; one inside a codepoint raises EINVAL."""
+        return _anchor_list(self.anchors_at_bytes_raw(positions, bias))
+
+    def resolve_anchors(self, anchors) -> list:
+        """[(id, bias)], made here or on any peer -> [(pos, pos_bytes, state)] in the visible
+        document now; state LIVE, DEAD (the item is tombstoned: the anchor lies where it was) or
+        UNKNOWN (the log does not hold the item yet) (crdt_hip_oplog_anchors_resolve)."""
+        return _anchor_pos_list(self.resolve_anchors_raw(anchors))
 
     def save(self, path: str) -> None:
         """Op-log file (crdt_hip_oplog_save): 64-byte-aligned SoA arrays."""
@@ -775,6 +883,15 @@ class Context:
                                          C.byref(ns)), self._h)
         return {"patches": int(p.value), "items": int(i.value), "tombstones": int(t.value),
                 "ranks": int(r.value), "device_ns": int(ns.value)}
+
+    def anchor_stats(self) -> dict:
+        """What this context's last Replica.anchors_at or resolve_anchors observed
+        (crdt_hip_anchor_stats)."""
+        a, u, r, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().crdt_hip_anchor_stats(self._h, C.byref(a), C.byref(u), C.byref(r),
+                                           C.byref(ns)), self._h)
+        return {"anchors": int(a.value), "unknown": int(u.value), "ranks": int(r.value),
+                "device_ns": int(ns.value)}
 
     def merge(self, log) -> tuple:
         """Merged document: (utf8 bytes, tree digest)."""
@@ -1109,6 +1226,33 @@ class Replica:
         """OpLog.patches_since_bytes on the device: the same patches."""
         return _patch_list(self.patches_since_bytes_raw(mark))
 
+    # Anchors (crdt_hip.h, "anchors"): the same arrays as the OpLog calls, byte for byte, from HIP
+    # kernels over the kept document order and its inverse.  A call leaves the replica as a
+    # merge_inc would and changes no log contents.
+    def anchors_at_raw(self, positions, bias=AFTER, out=None) -> np.ndarray:
+        return _anchors_at(lambda *a: lib().crdt_hip_replica_anchors_at(self.ctx._h, self._h, *a),
+                           positions, bias, self.ctx._h, out)
+
+    def anchors_at_bytes_raw(self, positions, bias=AFTER, out=None) -> np.ndarray:
+        return _anchors_at(lambda *a: lib().crdt_hip_replica_anchors_at_bytes(
+            self.ctx._h, self._h, *a), positions, bias, self.ctx._h, out)
+
+    def resolve_anchors_raw(self, anchors, out=None) -> np.ndarray:
+        return _anchors_resolve(lambda *a: lib().crdt_hip_replica_anchors_resolve(
+            self.ctx._h, self._h, *a), anchors, self.ctx._h, out)
+
+    def anchors_at(self, positions, bias=AFTER) -> list:
+        """OpLog.anchors_at on the device (crdt_hip_replica_anchors_at)."""
+        return _anchor_list(self.anchors_at_raw(positions, bias))
+
+    def anchors_at_bytes(self, positions, bias=AFTER) -> list:
+        """OpLog.anchors_at_bytes on the device (crdt_hip_replica_anchors_at_bytes)."""
+        return _anchor_list(self.anchors_at_bytes_raw(positions, bias))
+
+    def resolve_anchors(self, anchors) -> list:
+        """OpLog.resolve_anchors on the device (crdt_hip_replica_anchors_resolve)."""
+        return _anchor_pos_list(self.resolve_anchors_raw(anchors))
+
     def info(self) -> tuple:
         """(items, visible codepoints, visible UTF-8 bytes)."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -1255,6 +1399,18 @@ class HipMerge:
         finally:
             m.close()
 
+    def anchor_at(self, pos: int, bias: int = AFTER) -> tuple:
+        """A cursor at gap `pos` as (id, bias): a place that survives every later edit and sync and
+        means the same on every peer (OpLog.anchors_at)."""
+        return self.log.anchors_at([pos], bias)[0]
+
+    def resolve_many(self, anchors) -> list:
+        """Where each anchor lies now; None for one whose item this log does not hold yet."""
+        return [None if st == UNKNOWN else pos for pos, _, st in self.log.resolve_anchors(anchors)]
+
+    def resolve(self, anchor: tuple):
+        return self.resolve_many([anchor])[0]
+
 
 class HipDownstream:
     """`Downstream` (/root/reference/src/rope.rs:185-191) with the replica on the device.
@@ -1351,6 +1507,20 @@ class HipDownstream:
         finally:
             m.close()
 
+    def anchor_at(self, pos: int, bias: int = AFTER) -> tuple:
+        """HipMerge.anchor_at on the device: the queued updates are decoded first."""
+        self.flush()
+        return self.replica.anchors_at([pos], bias)[0]
+
+    def resolve_many(self, anchors) -> list:
+        """HipMerge.resolve_many on the device: the queued updates are decoded first."""
+        self.flush()
+        return [None if st == UNKNOWN else pos
+                for pos, _, st in self.replica.resolve_anchors(anchors)]
+
+    def resolve(self, anchor: tuple):
+        return self.resolve_many([anchor])[0]
+
     def text(self) -> str:
         self.flush()
         return self.replica.merge()[0].decode("utf-8")
@@ -1395,6 +1565,15 @@ class HipDownstreamBytes(HipDownstream):
     def patches_since(self, mark: Mark) -> list:
         self.flush()
         return self.replica.patches_since_bytes(mark)
+
+    def anchor_at(self, pos: int, bias: int = AFTER) -> tuple:
+        self.flush()
+        return self.replica.anchors_at_bytes([pos], bias)[0]
+
+    def resolve_many(self, anchors) -> list:
+        self.flush()
+        return [None if st == UNKNOWN else nbytes
+                for _, nbytes, st in self.replica.resolve_anchors(anchors)]
 
     def len(self) -> int:
         """UTF-8 bytes of the merged document: the merge's own count, cross-checked against the

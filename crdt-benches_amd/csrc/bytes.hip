@@ -175,10 +175,14 @@ __global__ __launch_bounds__(kOrdT) void k_bytes_table(BytesArgs a) {
 
 }  // namespace
 
-void bytes_translate_enqueue(const BytesArgs& a, hipStream_t s) {
+void bytes_count_enqueue(const BytesArgs& a, hipStream_t s) {
     k_bytes_init<<<grid_for(std::max<uint64_t>(a.np, B_N), kJB), kJB, 0, s>>>(a);
     k_bytes_count<<<a.ntiles, kOrdT, 0, s>>>(a);
     k_bytes_top<<<1, kOrdTop, 0, s>>>(a);
+}
+
+void bytes_translate_enqueue(const BytesArgs& a, hipStream_t s) {
+    bytes_count_enqueue(a, s);
     k_bytes_translate<<<a.ntiles, kOrdT, 0, s>>>(a);
     k_bytes_table<<<1, kOrdT, 0, s>>>(a);
 }

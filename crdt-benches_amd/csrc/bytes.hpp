@@ -33,6 +33,10 @@ struct BytesArgs {
     uint64_t* ctl;           // B_N counters
 };
 
+// Enqueues init, count and top alone: the counters cleared, tcount and tbpre the exclusive prefixes
+// of the tiles' visible items and bytes, B_VIS and B_VISB their totals.  With np == 0 nothing of a
+// patch is touched (anchor.hip counts and scans with it).
+void bytes_count_enqueue(const BytesArgs& a, hipStream_t s);
 // Enqueues the translation on `s`: init, count, top, translate, table.  The caller then waits
 // for ctl: B_STARTS or B_ENDS below np means a boundary inside a codepoint.
 void bytes_translate_enqueue(const BytesArgs& a, hipStream_t s);

@@ -35,6 +35,7 @@ struct crdt_hip_ctx {
     crdt::DeltaStats last_delta;  // what the last device encode_diff / apply_diff observed
     crdt::PatchStats last_patch;  // what the last device patches_since observed
     crdt::EditStats last_edit;    // what the last device apply_patches observed
+    crdt::AnchorStats last_anchor;  // what the last device anchors_at / anchors_resolve observed
 };
 namespace {
 // Names the owner of a mark: every log and replica handle gets its own, a clone included.
@@ -1192,6 +1193,77 @@ int crdt_hip_replica_patches_since_bytes(crdt_hip_ctx* ctx, crdt_hip_replica* r,
                                     ctx->eng, r->r, m->dev, reinterpret_cast<crdt::PatchRec*>(out), cap,
                                     out_n, ins, ins_cap, out_ins, &ctx->last_patch));
     });
+}
+// ---- anchors: cursor and selection positions that survive sync --------------------------------------
+static_assert(sizeof(crdt_hip_anchor) == sizeof(crdt::AnchorRec) && sizeof(crdt_hip_anchor) == 16 &&
+                  sizeof(crdt_hip_anchor_pos) == sizeof(crdt::AnchorPosRec) &&
+                  sizeof(crdt_hip_anchor_pos) == 24,
+              "anchor layouts");
+namespace {
+int oplog_anchors_at(crdt_hip_oplog* log, const uint64_t* pos, const uint8_t* bias, size_t n,
+                     bool bytes, crdt_hip_anchor* out) {
+    if (!log || ((!pos || !out) && n)) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    return guard(nullptr, [&] {
+        std::string e;
+        const int rc = log->log.anchors_at(pos, bias, n, bytes, reinterpret_cast<crdt::AnchorRec*>(out), e);
+        return rc ? set_err(nullptr, rc, e) : 0;
+    });
+}
+int replica_anchors_at(crdt_hip_ctx* ctx, crdt_hip_replica* r, const uint64_t* pos, const uint8_t* bias,
+                       size_t n, bool bytes, crdt_hip_anchor* out) {
+    if (!ctx || !r || ((!pos || !out) && n)) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    return guard(ctx, [&] {
+        return from_engine(ctx, crdt::replica_anchors_at(ctx->eng, r->r, pos, bias, n, bytes,
+                                                         reinterpret_cast<crdt::AnchorRec*>(out),
+                                                         &ctx->last_anchor));
+    });
+}
+}  // namespace
+int crdt_hip_oplog_anchors_at(crdt_hip_oplog* log, const uint64_t* pos, const uint8_t* bias, size_t n,
+                              crdt_hip_anchor* out) {
+    return oplog_anchors_at(log, pos, bias, n, false, out);
+}
+int crdt_hip_oplog_anchors_at_bytes(crdt_hip_oplog* log, const uint64_t* pos, const uint8_t* bias,
+                                    size_t n, crdt_hip_anchor* out) {
+    return oplog_anchors_at(log, pos, bias, n, true, out);
+}
+int crdt_hip_oplog_anchors_resolve(crdt_hip_oplog* log, const crdt_hip_anchor* a, size_t n,
+                                   crdt_hip_anchor_pos* out) {
+    if (!log || ((!a || !out) && n)) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    return guard(nullptr, [&] {
+        std::string e;
+        const int rc = log->log.anchors_resolve(reinterpret_cast<const crdt::AnchorRec*>(a), n,
+                                                reinterpret_cast<crdt::AnchorPosRec*>(out), e);
+        return rc ? set_err(nullptr, rc, e) : 0;
+    });
+}
+int crdt_hip_replica_anchors_at(crdt_hip_ctx* ctx, crdt_hip_replica* r, const uint64_t* pos,
+                                const uint8_t* bias, size_t n, crdt_hip_anchor* out) {
+    return replica_anchors_at(ctx, r, pos, bias, n, false, out);
+}
+int crdt_hip_replica_anchors_at_bytes(crdt_hip_ctx* ctx, crdt_hip_replica* r, const uint64_t* pos,
+                                      const uint8_t* bias, size_t n, crdt_hip_anchor* out) {
+    return replica_anchors_at(ctx, r, pos, bias, n, true, out);
+}
+int crdt_hip_replica_anchors_resolve(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_anchor* a,
+                                     size_t n, crdt_hip_anchor_pos* out) {
+    if (!ctx || !r || ((!a || !out) && n)) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    return guard(ctx, [&] {
+        return from_engine(ctx, crdt::replica_anchors_resolve(
+                                    ctx->eng, r->r, reinterpret_cast<const crdt::AnchorRec*>(a), n,
+                                    reinterpret_cast<crdt::AnchorPosRec*>(out), &ctx->last_anchor));
+    });
+}
+int crdt_hip_anchor_stats(const crdt_hip_ctx* ctx, uint64_t* anchors, uint64_t* unknown,
+                          uint64_t* ranks, uint64_t* device_ns) {
+    if (!ctx) return set_err(nullptr, CRDT_HIP_EINVAL, "null context");
+    if (anchors) *anchors = ctx->last_anchor.anchors;
+    if (unknown) *unknown = ctx->last_anchor.unknown;
+    if (ranks) *ranks = ctx->last_anchor.ranks;
+    if (device_ns) *device_ns = ctx->last_anchor.device_ns;
+    return 0;
 }
 int crdt_hip_replica_info(const crdt_hip_replica* r, uint64_t* items,
                           uint64_t* visible_codepoints, uint64_t* visible_bytes) {

@@ -74,6 +74,23 @@ std::vector<Patch> patches_get(Call&& call, crdt_hip_ctx* ctx, size_t cap0, size
     return out;
 }
 
+// A cursor, a selection end: a place in the text that survives every edit and sync and means the
+// same on every peer (crdt_hip_anchor; 16 plain bytes, shipped as they are).
+using Anchor = crdt_hip_anchor;
+// Where an anchor lies now (codepoints; HipDownstreamBytes: bytes), or nothing while the item it
+// names has not arrived (CRDT_HIP_ANCHOR_UNKNOWN): resolve again after the next sync.
+struct AnchorAt {
+    bool known;
+    size_t pos;
+};
+inline std::vector<AnchorAt> anchors_known(const std::vector<crdt_hip_anchor_pos>& p, bool bytes) {
+    std::vector<AnchorAt> out;
+    out.reserve(p.size());
+    for (const crdt_hip_anchor_pos& x : p)
+        out.push_back(AnchorAt{x.state != CRDT_HIP_ANCHOR_UNKNOWN, (size_t)(bytes ? x.pos_bytes : x.pos)});
+    return out;
+}
+
 class HipMerge {
 public:
     static constexpr const char* NAME = "mi355x";
@@ -183,6 +200,22 @@ public:
             },
             nullptr, 0, 0);
     }
+    // The anchor of gap `pos` (bias: CRDT_HIP_ANCHOR_AFTER sticks to the item before the gap,
+    // BEFORE to the one after it), and where anchors made here or on any peer lie now.
+    Anchor anchor_at(size_t pos, uint32_t bias = CRDT_HIP_ANCHOR_AFTER) const {
+        const uint64_t p = pos;
+        const uint8_t b = (uint8_t)bias;
+        Anchor a;
+        check(crdt_hip_oplog_anchors_at(log_.get(), &p, &b, 1, &a), nullptr, "oplog_anchors_at");
+        return a;
+    }
+    std::vector<AnchorAt> resolve_many(const std::vector<Anchor>& a) const {
+        std::vector<crdt_hip_anchor_pos> p(a.size());
+        check(crdt_hip_oplog_anchors_resolve(log_.get(), a.data(), a.size(), p.data()), nullptr,
+              "oplog_anchors_resolve");
+        return anchors_known(p, false);
+    }
+    AnchorAt resolve(const Anchor& a) const { return resolve_many({a})[0]; }
 
 private:
     struct Free {
@@ -285,8 +318,34 @@ public:
             },
             dev_->ctx, 4096, 1 << 16);
     }
+    // HipMerge::anchor_at / resolve / resolve_many on the device (the queued updates are decoded
+    // first): resolved in HIP kernels against the replica's kept document order.
+    Anchor anchor_at(size_t pos, uint32_t bias = CRDT_HIP_ANCHOR_AFTER) const {
+        return anchor_of(pos, bias, false);
+    }
+    std::vector<AnchorAt> resolve_many(const std::vector<Anchor>& a) const {
+        return anchors_known(resolved(a), false);
+    }
+    AnchorAt resolve(const Anchor& a) const { return resolve_many({a})[0]; }
 
 protected:
+    Anchor anchor_of(size_t pos, uint32_t bias, bool bytes) const {
+        flush();
+        const uint64_t p = pos;
+        const uint8_t b = (uint8_t)bias;
+        Anchor a;
+        check((bytes ? crdt_hip_replica_anchors_at_bytes
+                     : crdt_hip_replica_anchors_at)(dev_->ctx, rep_, &p, &b, 1, &a),
+              dev_->ctx, "replica_anchors_at");
+        return a;
+    }
+    std::vector<crdt_hip_anchor_pos> resolved(const std::vector<Anchor>& a) const {
+        flush();
+        std::vector<crdt_hip_anchor_pos> p(a.size());
+        check(crdt_hip_replica_anchors_resolve(dev_->ctx, rep_, a.data(), a.size(), p.data()),
+              dev_->ctx, "replica_anchors_resolve");
+        return p;
+    }
     std::shared_ptr<Device> dev_;
     crdt_hip_replica* rep_ = nullptr;
     mutable std::vector<uint8_t> buf_;
@@ -340,6 +399,14 @@ public:
             },
             dev_->ctx, 4096, 1 << 16);
     }
+    // Anchors taken at, and resolved to, byte offsets (one inside a codepoint is an error).
+    Anchor anchor_at(size_t pos, uint32_t bias = CRDT_HIP_ANCHOR_AFTER) const {
+        return anchor_of(pos, bias, true);
+    }
+    std::vector<AnchorAt> resolve_many(const std::vector<Anchor>& a) const {
+        return anchors_known(resolved(a), true);
+    }
+    AnchorAt resolve(const Anchor& a) const { return resolve_many({a})[0]; }
 };
 
 }  // namespace hipmerge

@@ -1208,4 +1208,16 @@ int replica_kept_order(Engine& E, Replica& r, const char* who, const uint32_t** 
     return CRDT_HIP_OK;
 }
 
+int replica_kept_ranks(Engine& E, Replica& r, const char* who, const uint32_t** seq,
+                       const uint32_t** rank, uint32_t* ntiles) {
+    const int rc = replica_kept_order(E, r, who, seq, ntiles);
+    if (rc) return rc;
+    *rank = r.inc.rank[r.inc.cur];  // (cap entries, as seq: checked above)
+    if (!*rank) {
+        E.err = std::string(who) + ": the kept document order has no inverse";
+        return CRDT_HIP_EBADLOG;
+    }
+    return CRDT_HIP_OK;
+}
+
 }  // namespace crdt

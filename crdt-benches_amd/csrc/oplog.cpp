@@ -858,6 +858,150 @@ int OpLog::patches_walk(const LogMark& m, bool bytes, std::vector<PatchRec>& out
     return CRDT_HIP_OK;
 }
 
+// ---- anchors -----------------------------------------------------------------------------------
+int anchor_check_at(const uint64_t* pos, const uint8_t* bias, size_t n, uint64_t visible,
+                    std::string& err) {
+    if (n >= (1ull << 31)) {
+        err = "2^31 or more anchors";
+        return CRDT_HIP_ERANGE;
+    }
+    for (size_t k = 0; k < n; ++k) {
+        if (bias && bias[k] > kAnchorBefore) {
+            err = "anchor bias is neither AFTER nor BEFORE";
+            return CRDT_HIP_EINVAL;
+        }
+        if (pos[k] > visible) {
+            err = "anchor position beyond the document";
+            return CRDT_HIP_ERANGE;
+        }
+    }
+    return CRDT_HIP_OK;
+}
+
+int anchor_check_resolve(const AnchorRec* a, size_t n, std::string& err) {
+    if (n >= (1ull << 31)) {
+        err = "2^31 or more anchors";
+        return CRDT_HIP_ERANGE;
+    }
+    for (size_t k = 0; k < n; ++k) {
+        if ((a[k].id >= kDeltaKeyEnd && a[k].id != kAnchorEdge) || a[k].bias > kAnchorBefore || a[k].pad) {
+            err = "malformed anchor";
+            return CRDT_HIP_EINVAL;
+        }
+    }
+    return CRDT_HIP_OK;
+}
+
+int OpLog::anchors_at(const uint64_t* pos, const uint8_t* bias, size_t n, bool bytes, AnchorRec* out,
+                      std::string& err) const {
+    const int rc = anchor_check_at(pos, bias, n, bytes ? visible_bytes() : nvis_, err);
+    if (rc || n == 0) return rc;
+    std::vector<uint32_t> order;
+    err = document_order(order);
+    if (!err.empty()) return CRDT_HIP_EBADLOG;
+    // vis[v - 1]: the v-th visible item; ends[v]: UTF-8 bytes of the first v visible items
+    std::vector<uint32_t> vis;
+    std::vector<uint64_t> ends;
+    vis.reserve((size_t)nvis_);
+    if (bytes) {
+        ends.reserve((size_t)nvis_ + 1);
+        ends.push_back(0);
+    }
+    for (uint32_t id : order) {
+        if (deleted[id - 1]) continue;
+        vis.push_back(id);
+        if (bytes) ends.push_back(ends.back() + utf8_len_cp(cp[id - 1]));
+    }
+    std::vector<AnchorRec> res(n);
+    for (size_t k = 0; k < n; ++k) {
+        uint64_t v = pos[k];  // visible items before the gap
+        if (bytes) {
+            const auto it = std::lower_bound(ends.begin(), ends.end(), v);
+            if (it == ends.end() || *it != v) {
+                err = "anchor position inside a codepoint";
+                return CRDT_HIP_EINVAL;
+            }
+            v = (uint64_t)(it - ends.begin());
+        }
+        const uint32_t b = bias ? bias[k] : kAnchorAfter;
+        const uint64_t item = b == kAnchorAfter ? v : v + 1;  // 1-based visible rank (0, len + 1: edge)
+        if (item > vis.size()) {
+            if (b == kAnchorAfter) {  // (anchor_check_at against a counter the log does not bear out)
+                err = "the visible items disagree with the log's counter";
+                return CRDT_HIP_EBADLOG;
+            }
+            res[k] = AnchorRec{kAnchorEdge, b, 0u};
+        } else if (item == 0) {
+            res[k] = AnchorRec{kAnchorEdge, b, 0u};
+        } else {
+            const uint32_t id = vis[item - 1];
+            res[k] = AnchorRec{((uint64_t)lamport[id - 1] << 16) | agent[id - 1], b, 0u};
+        }
+    }
+    std::memcpy(out, res.data(), n * sizeof(AnchorRec));
+    return CRDT_HIP_OK;
+}
+
+int OpLog::anchors_resolve(const AnchorRec* a, size_t n, AnchorPosRec* out, std::string& err) const {
+    const int rc = anchor_check_resolve(a, n, err);
+    if (rc || n == 0) return rc;
+    std::vector<uint32_t> order;
+    err = document_order(order);
+    if (!err.empty()) return CRDT_HIP_EBADLOG;
+    // the distinct identities asked for, sorted, and the slot that holds each (0: none; of two
+    // slots of a malformed log that share an identity, the lower)
+    std::vector<uint64_t> want;
+    want.reserve(n);
+    for (size_t k = 0; k < n; ++k)
+        if (a[k].id != kAnchorEdge) want.push_back(a[k].id);
+    std::sort(want.begin(), want.end());
+    want.erase(std::unique(want.begin(), want.end()), want.end());
+    std::vector<uint32_t> slot(want.size(), 0u);
+    if (!want.empty())
+        for (uint32_t id = 1; id <= size(); ++id) {
+            const uint64_t ident = ((uint64_t)lamport[id - 1] << 16) | agent[id - 1];
+            const auto it = std::lower_bound(want.begin(), want.end(), ident);
+            if (it != want.end() && *it == ident && !slot[it - want.begin()]) slot[it - want.begin()] = id;
+        }
+    // per wanted slot: the visible items, and their bytes, at the ranks before it
+    std::vector<uint64_t> before(want.size(), 0), before_b(want.size(), 0);
+    std::vector<uint32_t> at(size() + 1ull, ~0u);  // slot -> its index in `want`
+    for (size_t j = 0; j < want.size(); ++j)
+        if (slot[j]) at[slot[j]] = (uint32_t)j;
+    uint64_t v = 0, vb = 0;
+    for (uint32_t id : order) {
+        if (at[id] != ~0u) {
+            before[at[id]] = v;
+            before_b[at[id]] = vb;
+        }
+        if (!deleted[id - 1]) {
+            ++v;
+            vb += utf8_len_cp(cp[id - 1]);
+        }
+    }
+    std::vector<AnchorPosRec> res(n);
+    for (size_t k = 0; k < n; ++k) {
+        if (a[k].id == kAnchorEdge) {
+            res[k] = a[k].bias == kAnchorAfter ? AnchorPosRec{0, 0, kAnchorLive, 0u}
+                                               : AnchorPosRec{v, vb, kAnchorLive, 0u};
+            continue;
+        }
+        const size_t j = (size_t)(std::lower_bound(want.begin(), want.end(), a[k].id) - want.begin());
+        const uint32_t id = slot[j];
+        if (!id) {
+            res[k] = AnchorPosRec{0, 0, kAnchorUnknown, 0u};
+            continue;
+        }
+        const bool live = !deleted[id - 1];
+        const bool add = live && a[k].bias == kAnchorAfter;
+        res[k] = AnchorPosRec{before[j] + (add ? 1u : 0u),
+                              before_b[j] + (add ? utf8_len_cp(cp[id - 1]) : 0u),
+                              live ? kAnchorLive : kAnchorDead, 0u};
+    }
+    std::memcpy(out, res.data(), n * sizeof(AnchorPosRec));
+    return CRDT_HIP_OK;
+}
+
 // ---- local edits as positional patches ---------------------------------------------------------
 // The argument-only checks of a patch array, in codepoints or (BYTES) in UTF-8 bytes: `visible`
 // and the non-touching rule are in the unit of pos and del.  emit(old position, del, first

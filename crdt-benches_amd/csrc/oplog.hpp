@@ -133,6 +133,27 @@ struct EditPlanBytes {
 int edit_plan_bytes(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
                     uint64_t visible_bytes, uint64_t items, EditPlanBytes& plan, std::string& err);
 
+// Anchors (crdt_hip.h, "anchors"; the device twin is anchor.hip): a place in the text named by the
+// identity of the item next to it.  Layouts of crdt_hip_anchor and crdt_hip_anchor_pos.
+constexpr uint64_t kAnchorEdge = ~0ull;
+constexpr uint32_t kAnchorAfter = 0, kAnchorBefore = 1;
+constexpr uint32_t kAnchorLive = 0, kAnchorDead = 1, kAnchorUnknown = 2;
+struct AnchorRec {
+    uint64_t id;
+    uint32_t bias, pad;
+};
+struct AnchorPosRec {
+    uint64_t pos, pos_bytes;
+    uint32_t state, pad;
+};
+// The checks of the two calls that need no document, shared by the host and the device path, in
+// array order.  Create: per position a bias above 1 (EINVAL), then a position beyond `visible`
+// (codepoints or bytes, as pos counts; ERANGE).  Resolve: an id of 2^48 or more that is not the
+// edge, a bias above 1, pad != 0 (EINVAL).
+int anchor_check_at(const uint64_t* pos, const uint8_t* bias, size_t n, uint64_t visible,
+                    std::string& err);
+int anchor_check_resolve(const AnchorRec* a, size_t n, std::string& err);
+
 class OpLog {
 public:
     // ---- SoA (index k holds item id k+1) ----
@@ -229,6 +250,15 @@ public:
     // path is held to, not a product path: a call walks the whole document.
     int apply_patches_bytes(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
                             uint32_t* added, uint32_t* tombstoned, std::string& err);
+    // Anchors (crdt_hip.h, "anchors"): gap positions of the visible document -> identity-based
+    // anchors (pos in codepoints, or with `bytes` in UTF-8 bytes; bias null: all AFTER), and
+    // anchors -> where each lies now.  The definition the device path (anchor.hip) is held to: the
+    // order comes from document_order per call, O(items); the positional index is neither read nor
+    // touched.  Everything is validated before `out` is written.  EINVAL, ERANGE as crdt_hip.h
+    // states, EBADLOG for a malformed log.
+    int anchors_at(const uint64_t* pos, const uint8_t* bias, size_t n, bool bytes, AnchorRec* out,
+                   std::string& err) const;
+    int anchors_resolve(const AnchorRec* a, size_t n, AnchorPosRec* out, std::string& err) const;
     // Every item id in document order, tombstones included (RGA pre-order or Fugue in-order): the
     // sibling sort and walk that rebuild_index / rebuild_index_fugue build their index from.
     std::string document_order(std::vector<uint32_t>& order) const;

@@ -271,6 +271,30 @@ int replica_apply_patches_bytes(Engine& E, Replica& r, const PatchRec* p, size_t
 int replica_kept_order(Engine& E, Replica& r, const char* who, const uint32_t** seq,
                        uint32_t* ntiles);
 
+// replica_kept_order, and the inverse order with it: *rank = slot -> rank for slots 0..n, the array
+// the same merge_inc leaves (its splice writes a rank for every rank it writes a slot for).  Only
+// the sizes are checked here; a kernel that reads rank[s] checks the value against n and, where it
+// holds the slot anyway, seq[rank[s]] == s.
+int replica_kept_ranks(Engine& E, Replica& r, const char* who, const uint32_t** seq,
+                       const uint32_t** rank, uint32_t* ntiles);
+
+// Anchors (anchor.hip; semantics in crdt_hip.h, host twin OpLog::anchors_at / anchors_resolve).
+struct AnchorStats {  // what the last device anchors call observed (crdt_hip_anchor_stats)
+    uint64_t anchors = 0;    // anchors of the call
+    uint64_t unknown = 0;    // resolve: those whose identity the replica does not hold
+    uint64_t ranks = 0;      // ranks of the document order streamed (the items held)
+    uint64_t device_ns = 0;  // summed device time of the call's kernels (HIP events)
+};
+struct AnchorRec;
+struct AnchorPosRec;
+// Both settle a pending decode, check the arguments on the host (anchor_check_*), bring r.inc up to
+// date as replica_merge_inc does and wait once; `out` is written only by a call that succeeds.
+// bytes: pos counts UTF-8 bytes (a position inside a codepoint: EINVAL, found on the device).
+int replica_anchors_at(Engine& E, Replica& r, const uint64_t* pos, const uint8_t* bias, size_t n,
+                       bool bytes, AnchorRec* out, AnchorStats* stats = nullptr);
+int replica_anchors_resolve(Engine& E, Replica& r, const AnchorRec* a, size_t n, AnchorPosRec* out,
+                            AnchorStats* stats = nullptr);
+
 // Incremental merge (incr.hip): the merged text (may be null), its UTF-8 bytes and codepoints;
 // *path = 1 when only the items appended since the previous merge_inc were ranked, 0 for a
 // full merge (the first call, a concurrent update, more than kIncMax new items, Fugue).

@@ -35,6 +35,10 @@
  *   EDITS_USE_BYTE_OFFSETS = true (rope.rs:8,16-19; the cola and yrs adapters)
  *                        -> the *_bytes twins of replace, apply_patches and patches_since, on the
  *                           host and on the device ("byte offsets"): positions in UTF-8 bytes
+ *   a cursor or selection end that survives sync (cola's Anchor, yrs' StickyIndex, automerge's
+ *   cursors; no trait of the bench)
+ *                        -> crdt_hip_oplog_anchors_at / _anchors_resolve, or on the device
+ *                           crdt_hip_replica_anchors_at / _anchors_resolve ("anchors")
  *
  * Conventions
  *   - Every function returns int status: 0 = ok, < 0 = error (CRDT_HIP_E*).  Nothing throws or
@@ -501,6 +505,91 @@ int crdt_hip_replica_patches_since_bytes(crdt_hip_ctx* ctx, crdt_hip_replica* r,
                                          const crdt_hip_mark* m, crdt_hip_patch* out, size_t cap,
                                          size_t* out_n, uint8_t* ins, size_t ins_cap,
                                          size_t* out_ins);
+
+/* ---- anchors: cursor and selection positions that survive sync ----------------------------------
+ * A cursor, a selection end or a comment range is not an offset but a place in the text: it must
+ * keep pointing at the same place while every peer inserts and deletes around it, and mean the same
+ * place on every peer (cola's Anchor, yrs' StickyIndex, automerge's cursors).  An anchor names the
+ * item next to the gap by its identity, the 48-bit value of the delta layout (key[n] above), with a
+ * bias: AFTER is the gap right after the item, BEFORE the gap right before it.  EDGE with AFTER is
+ * the document start, EDGE with BEFORE the document end.  An anchor is 16 plain bytes and may be
+ * shipped to another peer as it is.
+ *
+ * Everything is defined over the document order of all items held, tombstones included (RGA
+ * pre-order or Fugue in-order, as for patches_since).  len = the visible codepoints.
+ *
+ * *_anchors_at: gap positions 0 <= p <= len of the current visible document -> anchors.  AFTER
+ * names the p-th visible item (p == 0: EDGE), BEFORE the (p + 1)-th (p == len: EDGE).
+ * *_anchors_at_bytes reads p in UTF-8 bytes: AFTER names the visible item whose inclusive UTF-8
+ * prefix equals p, BEFORE the one whose exclusive prefix equals p, the edges against the visible
+ * bytes.  bias == NULL means all AFTER.  Positions come in any order and may repeat.  Everything is
+ * validated before `out` is written (on an error it is untouched); n == 0 is ok.  The checks run in
+ * array order, per position the bias before the range, then, only when every position passed,
+ * the boundary check of the byte reading:
+ *   CRDT_HIP_EINVAL  a bias other than 0 or 1
+ *   CRDT_HIP_ERANGE  p beyond the document
+ *   CRDT_HIP_EINVAL  (bytes) p inside a codepoint
+ *
+ * *_anchors_resolve: anchors, made here or on any other peer -> where each lies now.  For an anchor
+ * on item x: pos = the visible items at ranks strictly before rank(x), plus 1 if the bias is AFTER
+ * and x is visible; pos_bytes the same with UTF-8 lengths as weights; state LIVE or DEAD by x's
+ * tombstone.  A DEAD anchor lies where its item was, the same place under either bias.
+ * EDGE / AFTER gives (0, 0, LIVE), EDGE / BEFORE (len, visible bytes, LIVE).  An identity the log
+ * does not hold is no error: it gives (0, 0, UNKNOWN), since a remote cursor may arrive before the
+ * update that carries its item, and the caller resolves it again after the next sync.  Anchors
+ * come in any order and may repeat.
+ *   CRDT_HIP_EINVAL  an id of 2^48 or more that is not EDGE; a bias above 1; pad != 0; a replica of
+ *                    another context
+ * Hence resolve(anchors_at(p, b)) == p; after an insert of k codepoints at the very gap p an AFTER
+ * anchor stays at p and a BEFORE anchor moves to p + k; after the anchored item is deleted the
+ * anchor is DEAD at the same pos; and two logs that hold the same items resolve an anchor alike,
+ * whatever their slot numbering.
+ *
+ * The host calls are the definition, not a product path: they take the order from the log itself
+ * per call, O(items), and neither read nor disturb the resolver index; a malformed log is
+ * CRDT_HIP_EBADLOG.  The device calls are the product, with byte-identical results.  They settle a
+ * pending decode and bring the kept document order up to date exactly as
+ * crdt_hip_replica_patches_since does (so a call leaves the replica as a merge_inc would), make no
+ * host copy of the replica's columns, wait for the host once and change no log contents.  Both
+ * count the visible codepoints and UTF-8 bytes per tile of 4,096 ranks and scan the tile aggregates
+ * (64-bit byte prefixes).  Resolve then enters the batch's distinct identities into a hash table,
+ * probes it with every key of the replica, and per anchor (a wave each) takes the item's rank from
+ * the kept inverse order and counts the visible ranks of its tile before it.  Create searches the
+ * scanned prefixes for each position's tile and walks that tile, a wave per position, to the item.
+ * Known cost: a call streams every rank of the replica once, and for a resolve every key as well,
+ * however few the anchors; after a join or a delta it first pays the full ORDER-mode rebuild. */
+#define CRDT_HIP_ANCHOR_EDGE 0xFFFFFFFFFFFFFFFFull
+enum { CRDT_HIP_ANCHOR_AFTER = 0, CRDT_HIP_ANCHOR_BEFORE = 1 };
+enum { CRDT_HIP_ANCHOR_LIVE = 0, CRDT_HIP_ANCHOR_DEAD = 1, CRDT_HIP_ANCHOR_UNKNOWN = 2 };
+typedef struct {
+    uint64_t id;    /* identity lamport << 16 | agent (no Fugue side bit), or CRDT_HIP_ANCHOR_EDGE */
+    uint32_t bias;  /* AFTER: the gap right after the item; BEFORE: the gap right before it */
+    uint32_t pad;   /* 0 */
+} crdt_hip_anchor;
+typedef struct {
+    uint64_t pos;        /* codepoints before the anchor in the visible document */
+    uint64_t pos_bytes;  /* UTF-8 bytes before it */
+    uint32_t state;      /* LIVE, DEAD (the item is tombstoned), UNKNOWN (the log lacks the item) */
+    uint32_t pad;        /* 0 */
+} crdt_hip_anchor_pos;
+int crdt_hip_oplog_anchors_at(crdt_hip_oplog* log, const uint64_t* pos, const uint8_t* bias, size_t n,
+                              crdt_hip_anchor* out);
+int crdt_hip_oplog_anchors_at_bytes(crdt_hip_oplog* log, const uint64_t* pos, const uint8_t* bias,
+                                    size_t n, crdt_hip_anchor* out);
+int crdt_hip_oplog_anchors_resolve(crdt_hip_oplog* log, const crdt_hip_anchor* a, size_t n,
+                                   crdt_hip_anchor_pos* out);
+int crdt_hip_replica_anchors_at(crdt_hip_ctx* ctx, crdt_hip_replica* r, const uint64_t* pos,
+                                const uint8_t* bias, size_t n, crdt_hip_anchor* out);
+int crdt_hip_replica_anchors_at_bytes(crdt_hip_ctx* ctx, crdt_hip_replica* r, const uint64_t* pos,
+                                      const uint8_t* bias, size_t n, crdt_hip_anchor* out);
+int crdt_hip_replica_anchors_resolve(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_anchor* a,
+                                     size_t n, crdt_hip_anchor_pos* out);
+/* What the context's last device anchors call observed (each may be NULL): anchors of the call,
+ * those that resolved UNKNOWN (0 for a create), ranks of the document order streamed (the items
+ * held), and the summed device time of the call's own kernels in ns (HIP events; the order update
+ * is not included). */
+int crdt_hip_anchor_stats(const crdt_hip_ctx* ctx, uint64_t* anchors, uint64_t* unknown,
+                          uint64_t* ranks, uint64_t* device_ns);
 
 /* ---- trace loader (crdt-testdata load_testing_data / chars_to_bytes, main.rs:19-23) ---------- */
 int crdt_hip_trace_load(const char* path, crdt_hip_trace** out);
