@@ -67,6 +67,7 @@ EXPORTS = [
     "crdt_hip_oplog_anchors_resolve", "crdt_hip_replica_anchors_at",
     "crdt_hip_replica_anchors_at_bytes", "crdt_hip_replica_anchors_resolve",
     "crdt_hip_anchor_stats",
+    "crdt_hip_oplog_spans", "crdt_hip_replica_spans", "crdt_hip_format_stats",
 ]
 
 
@@ -216,6 +217,9 @@ def lib() -> C.CDLL:
         "crdt_hip_replica_anchors_at_bytes": (i32, [vp, vp, vp, vp, sz, vp]),
         "crdt_hip_replica_anchors_resolve": (i32, [vp, vp, vp, sz, vp]),
         "crdt_hip_anchor_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64)]),
+        "crdt_hip_oplog_spans": (i32, [vp, vp, sz, vp, sz, P(sz), vp, sz, P(sz), P(sz)]),
+        "crdt_hip_replica_spans": (i32, [vp, vp, vp, sz, vp, sz, P(sz), vp, sz, P(sz), P(sz)]),
+        "crdt_hip_format_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge": (i32, [vp, vp, vp, sz, P(sz), P(u64)]),
         "crdt_hip_replica_merge_len": (i32, [vp, vp, P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge_inc": (i32, [vp, vp, vp, sz, P(sz), P(u64), P(u32)]),
@@ -486,6 +490,63 @@ def _anchor_pos_list(raw: np.ndarray) -> list:
     return [(int(p["pos"]), int(p["pos_bytes"]), int(p["state"])) for p in raw]
 
 
+# Formats (crdt_hip.h, "formats"): attribute ranges between two anchors, flattened into spans.
+REMOVE = 1
+FORMAT_DTYPE = np.dtype([("start", ANCHOR_DTYPE), ("end", ANCHOR_DTYPE), ("op", "<u8"),
+                         ("value", "<u8"), ("key", "<u4"), ("flags", "<u4")])
+SPAN_DTYPE = np.dtype([("pos", "<u8"), ("pos_bytes", "<u8"), ("len", "<u8"), ("len_bytes", "<u8"),
+                       ("attr_off", "<u4"), ("attr_n", "<u4")])
+SPAN_ATTR_DTYPE = np.dtype([("value", "<u8"), ("key", "<u4"), ("pad", "<u4")])
+assert FORMAT_DTYPE.itemsize == 56 and SPAN_DTYPE.itemsize == 40 and SPAN_ATTR_DTYPE.itemsize == 16
+
+
+def _formats_pack(formats) -> np.ndarray:
+    """[(start, end, key, value, op, flags)] with start and end as (id, bias), or a structured
+    array of FORMAT_DTYPE (passed through unchecked)."""
+    if isinstance(formats, np.ndarray) and formats.dtype == FORMAT_DTYPE:
+        return np.ascontiguousarray(formats)
+    flist = list(formats)
+    arr = np.zeros(len(flist), FORMAT_DTYPE)
+    for k, (start, end, key, value, op, flags) in enumerate(flist):
+        arr[k] = ((start[0], start[1], 0), (end[0], end[1], 0), op, value, key, flags)
+    return arr
+
+
+def _spans_get(call, formats, ctx=None, out=None) -> tuple:
+    """call(f, n, out, cap, out_n, attrs, attr_cap, out_attrs, pending) under the ESPACE
+    convention -> (crdt_hip_span array, crdt_hip_span_attr array, pending).  `out`: a pair of
+    arrays to write into, tried once (a failed call leaves them untouched)."""
+    arr = _formats_pack(formats)
+    n, na, pend = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+
+    def once(sp, at):
+        return call(arr.ctypes.data if arr.size else None, arr.size,
+                    sp.ctypes.data if sp.size else None, sp.size, C.byref(n),
+                    at.ctypes.data if at.size else None, at.size, C.byref(na), C.byref(pend))
+
+    if out is not None:
+        sp, at = out
+        assert sp.dtype == SPAN_DTYPE and at.dtype == SPAN_ATTR_DTYPE
+        _check(once(sp, at), ctx)
+        return sp[: n.value], at[: na.value], int(pend.value)
+    sp, at = np.zeros(0, SPAN_DTYPE), np.zeros(0, SPAN_ATTR_DTYPE)
+    rc = once(sp, at)
+    if rc == -6:
+        sp, at = np.zeros(n.value, SPAN_DTYPE), np.zeros(na.value, SPAN_ATTR_DTYPE)
+        rc = once(sp, at)
+    _check(rc, ctx)
+    return sp[: n.value], at[: na.value], int(pend.value)
+
+
+def _span_list(raw: tuple) -> tuple:
+    """(spans, attrs, pending) -> ([(pos, len, pos_bytes, len_bytes, {key: value})], pending)."""
+    sp, at, pend = raw
+    return [(int(x["pos"]), int(x["len"]), int(x["pos_bytes"]), int(x["len_bytes"]),
+             {int(a["key"]): int(a["value"])
+              for a in at[int(x["attr_off"]): int(x["attr_off"]) + int(x["attr_n"])]})
+            for x in sp], pend
+
+
 class OpLog:
     """Host-side resolver (positional patches -> anchor op log), crdt_hip_oplog_*."""
 
@@ -697,6 +758,17 @@ class OpLog:
         UNKNOWN (the log does not hold the item yet) (crdt_hip_oplog_anchors_resolve)."""
         return _anchor_pos_list(self.resolve_anchors_raw(anchors))
 
+    # Formats (crdt_hip.h, "formats").  The host call is the definition the device call is held to.
+    def spans_raw(self, formats, out=None) -> tuple:
+        return _spans_get(lambda *a: lib().crdt_hip_oplog_spans(self._h, *a), formats, out=out)
+
+    def spans(self, formats) -> tuple:
+        """Attribute ranges [(start, end, key, value, op, flags)] (start, end: anchors (id, bias);
+        flags 0 or REMOVE) -> ([(pos, len, pos_bytes, len_bytes, {key: value})], pending): the
+        non-overlapping spans of the visible document, per key the covering format with the largest
+        op winning, and the formats whose anchors this log cannot place yet (crdt_hip_oplog_spans)."""
+        return _span_list(self.spans_raw(formats))
+
     def save(self, path: str) -> None:
         """Op-log file (crdt_hip_oplog_save): 64-byte-aligned SoA arrays."""
         _check(lib().crdt_hip_oplog_save(self._h, path.encode()))
@@ -892,6 +964,13 @@ class Context:
                                            C.byref(ns)), self._h)
         return {"anchors": int(a.value), "unknown": int(u.value), "ranks": int(r.value),
                 "device_ns": int(ns.value)}
+
+    def format_stats(self) -> dict:
+        """What this context's last Replica.spans observed (crdt_hip_format_stats)."""
+        v = [C.c_uint64() for _ in range(6)]
+        _check(lib().crdt_hip_format_stats(self._h, *[C.byref(x) for x in v]), self._h)
+        names = ("formats", "pending", "segments", "spans", "ranks", "device_ns")
+        return {k: int(x.value) for k, x in zip(names, v)}
 
     def merge(self, log) -> tuple:
         """Merged document: (utf8 bytes, tree digest)."""
@@ -1253,6 +1332,16 @@ class Replica:
         """OpLog.resolve_anchors on the device (crdt_hip_replica_anchors_resolve)."""
         return _anchor_pos_list(self.resolve_anchors_raw(anchors))
 
+    # Formats (crdt_hip.h, "formats"): the same arrays as OpLog.spans_raw, byte for byte, from HIP
+    # kernels over the kept document order.
+    def spans_raw(self, formats, out=None) -> tuple:
+        return _spans_get(lambda *a: lib().crdt_hip_replica_spans(self.ctx._h, self._h, *a), formats,
+                          self.ctx._h, out)
+
+    def spans(self, formats) -> tuple:
+        """OpLog.spans on the device (crdt_hip_replica_spans)."""
+        return _span_list(self.spans_raw(formats))
+
     def info(self) -> tuple:
         """(items, visible codepoints, visible UTF-8 bytes)."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -1303,7 +1392,71 @@ class Replica:
         return int(c.value), int(n.value), int(d.value)
 
 
-class HipMerge:
+class _RichText:
+    """Formats on an adapter (crdt_hip.h, "formats"): the adapter keeps its format ops in a dict by
+    op, makes their anchors where its document lies, and paints spans in its own unit.  Formats
+    travel beside the text, never in it: sync_formats_from is the union of two dicts."""
+
+    START, END = 1, 2  # `expand` bits: text typed at that edge of the range joins it
+    agent = 0          # the low 16 bits of this peer's format ops (set_agent)
+
+    def _rt_peer(self):  # what holds the document: an OpLog or a Replica, up to date
+        raise NotImplementedError
+
+    def _rt_anchors(self, positions, bias) -> list:
+        return self._rt_peer().anchors_at(positions, bias)
+
+    def set_agent(self, agent: int) -> None:
+        """This peer's agent id, for its later text edits and its later format ops alike."""
+        self._rt_peer().set_agent(agent)
+        self.agent = agent
+
+    @property
+    def formats(self) -> dict:
+        """{op: (start, end, key, value, flags)}, start and end as anchors (id, bias)."""
+        if "_formats" not in self.__dict__:
+            self._formats = {}
+        return self._formats
+
+    def _rt_add(self, start: int, end: int, key: int, value: int, flags: int, expand: int) -> int:
+        peer = self._rt_peer()
+        a = self._rt_anchors([start, end], [AFTER if expand & self.START else BEFORE,
+                                            BEFORE if expand & self.END else AFTER])
+        clock = max(max((lam for _, lam in peer.state_vector()), default=0),
+                    self.__dict__.get("_format_clock", 0)) + 1
+        self._format_clock = clock
+        op = (clock << 16) | self.agent
+        self.formats[op] = (a[0], a[1], key, value, flags)
+        return op
+
+    def format(self, start: int, end: int, key: int, value: int, expand: int = 0) -> int:
+        """Give the text between the gaps `start` and `end` the attribute (key, value); returns the
+        op.  `expand`: START | END, the edges at which text typed later joins the range."""
+        return self._rt_add(start, end, key, value, 0, expand)
+
+    def unformat(self, start: int, end: int, key: int, expand: int = 0) -> int:
+        """Take attribute `key` off the text between the gaps `start` and `end`; returns the op."""
+        return self._rt_add(start, end, key, 0, REMOVE, expand)
+
+    def sync_formats_from(self, other) -> int:
+        """Take the format ops of `other` that this peer lacks; returns how many."""
+        new = {op: f for op, f in other.formats.items() if op not in self.formats}
+        self.formats.update(new)
+        return len(new)
+
+    def _rt_unit(self, span: tuple) -> tuple:
+        pos, ln, _, _, attrs = span
+        return pos, ln, attrs
+
+    def spans(self) -> tuple:
+        """([(pos, len, {key: value})] in this adapter's unit, pending): what an editor paints,
+        and the formats whose anchors this peer cannot place until its next text sync."""
+        sp, pend = self._rt_peer().spans(
+            [(f[0], f[1], f[2], f[3], op, f[4]) for op, f in sorted(self.formats.items())])
+        return [self._rt_unit(x) for x in sp], pend
+
+
+class HipMerge(_RichText):
     """Mirror of the reference's per-CRDT adapter for the GPU engine.
 
     `Upstream` (/root/reference/src/rope.rs:6-33): NAME, EDITS_USE_BYTE_OFFSETS, from_str,
@@ -1411,8 +1564,11 @@ class HipMerge:
     def resolve(self, anchor: tuple):
         return self.resolve_many([anchor])[0]
 
+    def _rt_peer(self) -> OpLog:
+        return self.log
 
-class HipDownstream:
+
+class HipDownstream(_RichText):
     """`Downstream` (/root/reference/src/rope.rs:185-191) with the replica on the device.
 
     apply_update() queues the encoded update on the host; len() decodes every queued update on
@@ -1521,6 +1677,10 @@ class HipDownstream:
     def resolve(self, anchor: tuple):
         return self.resolve_many([anchor])[0]
 
+    def _rt_peer(self) -> Replica:
+        self.flush()
+        return self.replica
+
     def text(self) -> str:
         self.flush()
         return self.replica.merge()[0].decode("utf-8")
@@ -1574,6 +1734,13 @@ class HipDownstreamBytes(HipDownstream):
         self.flush()
         return [None if st == UNKNOWN else nbytes
                 for _, nbytes, st in self.replica.resolve_anchors(anchors)]
+
+    def _rt_anchors(self, positions, bias) -> list:
+        return self._rt_peer().anchors_at_bytes(positions, bias)
+
+    def _rt_unit(self, span: tuple) -> tuple:
+        _, _, pos, ln, attrs = span
+        return pos, ln, attrs
 
     def len(self) -> int:
         """UTF-8 bytes of the merged document: the merge's own count, cross-checked against the

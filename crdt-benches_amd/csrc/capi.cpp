@@ -36,6 +36,7 @@ struct crdt_hip_ctx {
     crdt::PatchStats last_patch;  // what the last device patches_since observed
     crdt::EditStats last_edit;    // what the last device apply_patches observed
     crdt::AnchorStats last_anchor;  // what the last device anchors_at / anchors_resolve observed
+    crdt::FormatStats last_format;  // what the last device spans observed
 };
 namespace {
 // Names the owner of a mark: every log and replica handle gets its own, a clone included.
@@ -1263,6 +1264,64 @@ int crdt_hip_anchor_stats(const crdt_hip_ctx* ctx, uint64_t* anchors, uint64_t* 
     if (unknown) *unknown = ctx->last_anchor.unknown;
     if (ranks) *ranks = ctx->last_anchor.ranks;
     if (device_ns) *device_ns = ctx->last_anchor.device_ns;
+    return 0;
+}
+// ---- formats: rich-text attribute ranges on anchors, flattened into spans ---------------------------
+static_assert(sizeof(crdt_hip_format) == sizeof(crdt::FormatRec) && sizeof(crdt_hip_format) == 56 &&
+                  sizeof(crdt_hip_span) == sizeof(crdt::SpanRec) && sizeof(crdt_hip_span) == 40 &&
+                  sizeof(crdt_hip_span_attr) == sizeof(crdt::SpanAttrRec) &&
+                  sizeof(crdt_hip_span_attr) == 16,
+              "format layouts");
+int crdt_hip_oplog_spans(crdt_hip_oplog* log, const crdt_hip_format* f, size_t n, crdt_hip_span* out,
+                         size_t cap, size_t* out_n, crdt_hip_span_attr* attrs, size_t attr_cap,
+                         size_t* out_attrs, size_t* pending) {
+    if (!log || (!f && n) || !out_n || !out_attrs || !pending)
+        return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    return guard(nullptr, [&] {
+        std::vector<crdt::SpanRec> sp;
+        std::vector<crdt::SpanAttrRec> at;
+        uint64_t pend = 0;
+        std::string e;
+        const int rc = log->log.spans(reinterpret_cast<const crdt::FormatRec*>(f), n, sp, at, pend, e);
+        if (rc) return set_err(nullptr, rc, e);
+        if (!sp.empty() && (!out || cap < sp.size() || !attrs || attr_cap < at.size())) {
+            *out_n = sp.size();
+            *out_attrs = at.size();
+            return set_err(nullptr, CRDT_HIP_ESPACE, "buffer too small");
+        }
+        if (!sp.empty()) {
+            std::memcpy(out, sp.data(), sp.size() * sizeof(crdt::SpanRec));
+            std::memcpy(attrs, at.data(), at.size() * sizeof(crdt::SpanAttrRec));
+        }
+        *out_n = sp.size();
+        *out_attrs = at.size();
+        *pending = (size_t)pend;
+        return 0;
+    });
+}
+int crdt_hip_replica_spans(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_format* f, size_t n,
+                           crdt_hip_span* out, size_t cap, size_t* out_n, crdt_hip_span_attr* attrs,
+                           size_t attr_cap, size_t* out_attrs, size_t* pending) {
+    if (!ctx || !r || (!f && n) || !out_n || !out_attrs || !pending)
+        return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    return guard(ctx, [&] {
+        return from_engine(ctx, crdt::replica_spans(
+                                    ctx->eng, r->r, reinterpret_cast<const crdt::FormatRec*>(f), n,
+                                    reinterpret_cast<crdt::SpanRec*>(out), cap, out_n,
+                                    reinterpret_cast<crdt::SpanAttrRec*>(attrs), attr_cap, out_attrs,
+                                    pending, &ctx->last_format));
+    });
+}
+int crdt_hip_format_stats(const crdt_hip_ctx* ctx, uint64_t* formats, uint64_t* pending,
+                          uint64_t* segments, uint64_t* spans, uint64_t* ranks, uint64_t* device_ns) {
+    if (!ctx) return set_err(nullptr, CRDT_HIP_EINVAL, "null context");
+    if (formats) *formats = ctx->last_format.formats;
+    if (pending) *pending = ctx->last_format.pending;
+    if (segments) *segments = ctx->last_format.segments;
+    if (spans) *spans = ctx->last_format.spans;
+    if (ranks) *ranks = ctx->last_format.ranks;
+    if (device_ns) *device_ns = ctx->last_format.device_ns;
     return 0;
 }
 int crdt_hip_replica_info(const crdt_hip_replica* r, uint64_t* items,

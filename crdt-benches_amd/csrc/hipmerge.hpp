@@ -6,8 +6,10 @@
 //   trait Downstream /root/reference/src/rope.rs:185-191
 //   Dt adapter it sits beside: /root/reference/src/rope.rs:105-137, :193-225
 #pragma once
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <memory>
 #include <string>
 #include <string_view>
@@ -88,6 +90,72 @@ inline std::vector<AnchorAt> anchors_known(const std::vector<crdt_hip_anchor_pos
     out.reserve(p.size());
     for (const crdt_hip_anchor_pos& x : p)
         out.push_back(AnchorAt{x.state != CRDT_HIP_ANCHOR_UNKNOWN, (size_t)(bytes ? x.pos_bytes : x.pos)});
+    return out;
+}
+
+// Rich text (crdt_hip.h, "formats"): attribute ranges between two anchors, last writer wins per key
+// by op.  Formats travel beside the text, never in it: an adapter keeps its format ops by op, and
+// sync_formats_from is the union of two such maps.
+using Format = crdt_hip_format;
+enum : unsigned { EXPAND_START = 1, EXPAND_END = 2 };  // text typed at that edge joins the range
+// A maximal run of visible text with one attribute set (pos, len in codepoints;
+// HipDownstreamBytes: bytes), its attributes ascending by key.
+struct Span {
+    size_t pos, len;
+    std::vector<std::pair<uint32_t, uint64_t>> attrs;
+};
+struct Spans {
+    std::vector<Span> spans;
+    size_t pending;  // formats whose anchors name an item that has not arrived: ask again after a sync
+};
+struct FormatSet {
+    std::map<uint64_t, Format> ops;  // by op
+    uint64_t clock = 0;              // of this peer's last format
+    uint16_t agent = 0;              // the low 16 bits of its ops
+    // The next op: the clock passes the largest lamport of the text's state vector and the last format.
+    uint64_t next_op(const std::vector<crdt_hip_sv_entry>& sv) {
+        for (const crdt_hip_sv_entry& e : sv) clock = std::max<uint64_t>(clock, e.lamport);
+        return (++clock << 16) | agent;
+    }
+    uint64_t add(const Anchor& start, const Anchor& end, uint32_t key, uint64_t value, uint32_t flags,
+                 const std::vector<crdt_hip_sv_entry>& sv) {
+        const uint64_t op = next_op(sv);
+        ops[op] = Format{start, end, op, value, key, flags};
+        return op;
+    }
+    size_t merge(const FormatSet& o) {
+        const size_t before = ops.size();
+        ops.insert(o.ops.begin(), o.ops.end());
+        return ops.size() - before;
+    }
+    std::vector<Format> list() const {
+        std::vector<Format> f;
+        f.reserve(ops.size());
+        for (const auto& kv : ops) f.push_back(kv.second);
+        return f;
+    }
+};
+// call(f, n, out, cap, out_n, attrs, attr_cap, out_attrs, pending) under the ESPACE convention.
+template <class Call>
+Spans spans_get(Call&& call, const FormatSet& set, crdt_hip_ctx* ctx, bool bytes) {
+    const std::vector<Format> f = set.list();
+    std::vector<crdt_hip_span> sp;
+    std::vector<crdt_hip_span_attr> at;
+    size_t n = 0, na = 0, pend = 0;
+    int rc = call(f.data(), f.size(), sp.data(), sp.size(), &n, at.data(), at.size(), &na, &pend);
+    if (rc == CRDT_HIP_ESPACE) {
+        sp.resize(n);
+        at.resize(na);
+        rc = call(f.data(), f.size(), sp.data(), sp.size(), &n, at.data(), at.size(), &na, &pend);
+    }
+    check(rc, ctx, "spans");
+    Spans out{{}, pend};
+    for (size_t k = 0; k < n; ++k) {
+        Span s{(size_t)(bytes ? sp[k].pos_bytes : sp[k].pos), (size_t)(bytes ? sp[k].len_bytes : sp[k].len), {}};
+        for (uint32_t q = 0; q < sp[k].attr_n; ++q)
+            s.attrs.push_back({at[sp[k].attr_off + q].key, at[sp[k].attr_off + q].value});
+        out.spans.push_back(std::move(s));
+    }
     return out;
 }
 
@@ -216,8 +284,42 @@ public:
         return anchors_known(p, false);
     }
     AnchorAt resolve(const Anchor& a) const { return resolve_many({a})[0]; }
+    // Rich text: give the text between the gaps `start` and `end` the attribute (key, value), or
+    // take `key` off it; returns the op.  The start anchor is AFTER if EXPAND_START is set, else
+    // BEFORE; the end BEFORE if EXPAND_END is set, else AFTER.
+    void set_agent(uint16_t agent) {
+        check(crdt_hip_oplog_set_agent(log_.get(), agent), nullptr, "set_agent");
+        formats_.agent = agent;
+    }
+    uint64_t format(size_t start, size_t end, uint32_t key, uint64_t value, unsigned expand = 0) {
+        return format_op(start, end, key, value, 0, expand);
+    }
+    uint64_t unformat(size_t start, size_t end, uint32_t key, unsigned expand = 0) {
+        return format_op(start, end, key, 0, CRDT_HIP_FORMAT_REMOVE, expand);
+    }
+    Spans spans() const {
+        return spans_get(
+            [&](const Format* f, size_t n, crdt_hip_span* out, size_t cap, size_t* on,
+                crdt_hip_span_attr* at, size_t acap, size_t* oa, size_t* pend) {
+                return crdt_hip_oplog_spans(log_.get(), f, n, out, cap, on, at, acap, oa, pend);
+            },
+            formats_, nullptr, false);
+    }
+    const FormatSet& formats() const { return formats_; }
+    size_t sync_formats_from(const HipMerge& o) { return formats_.merge(o.formats_); }
 
 private:
+    uint64_t format_op(size_t start, size_t end, uint32_t key, uint64_t value, uint32_t flags,
+                       unsigned expand) {
+        std::vector<crdt_hip_sv_entry> sv(65536);
+        size_t n = 0;
+        check(crdt_hip_oplog_state_vector(log_.get(), sv.data(), sv.size(), &n), nullptr, "state_vector");
+        sv.resize(n);
+        return formats_.add(anchor_at(start, expand & EXPAND_START ? CRDT_HIP_ANCHOR_AFTER : CRDT_HIP_ANCHOR_BEFORE),
+                            anchor_at(end, expand & EXPAND_END ? CRDT_HIP_ANCHOR_BEFORE : CRDT_HIP_ANCHOR_AFTER),
+                            key, value, flags, sv);
+    }
+    FormatSet formats_;
     struct Free {
         void operator()(crdt_hip_oplog* l) const { crdt_hip_oplog_free(l); }
     };
@@ -256,7 +358,8 @@ public:
         return {std::move(d), std::move(pr.second)};
     }
     HipDownstream(HipDownstream&& o) noexcept
-        : dev_(std::move(o.dev_)), rep_(o.rep_), buf_(std::move(o.buf_)), off_(std::move(o.off_)) {
+        : formats_(std::move(o.formats_)), dev_(std::move(o.dev_)), rep_(o.rep_), buf_(std::move(o.buf_)),
+          off_(std::move(o.off_)) {
         o.rep_ = nullptr;
     }
     HipDownstream(const HipDownstream&) = delete;
@@ -327,8 +430,46 @@ public:
         return anchors_known(resolved(a), false);
     }
     AnchorAt resolve(const Anchor& a) const { return resolve_many({a})[0]; }
+    // HipMerge::format / unformat / spans / sync_formats_from on the device (the queued updates are
+    // decoded first): the spans come from HIP kernels over the replica's kept document order.
+    void set_agent(uint16_t agent) {
+        check(crdt_hip_replica_set_agent(rep_, agent), dev_->ctx, "replica_set_agent");
+        formats_.agent = agent;
+    }
+    uint64_t format(size_t start, size_t end, uint32_t key, uint64_t value, unsigned expand = 0) {
+        return format_op(start, end, key, value, 0, expand, false);
+    }
+    uint64_t unformat(size_t start, size_t end, uint32_t key, unsigned expand = 0) {
+        return format_op(start, end, key, 0, CRDT_HIP_FORMAT_REMOVE, expand, false);
+    }
+    Spans spans() const { return spans_of(false); }
+    const FormatSet& formats() const { return formats_; }
+    size_t sync_formats_from(const HipDownstream& o) { return formats_.merge(o.formats_); }
 
 protected:
+    uint64_t format_op(size_t start, size_t end, uint32_t key, uint64_t value, uint32_t flags,
+                       unsigned expand, bool bytes) {
+        flush();
+        std::vector<crdt_hip_sv_entry> sv(65536);
+        size_t n = 0;
+        check(crdt_hip_replica_state_vector(dev_->ctx, rep_, sv.data(), sv.size(), &n), dev_->ctx,
+              "replica_state_vector");
+        sv.resize(n);
+        return formats_.add(
+            anchor_of(start, expand & EXPAND_START ? CRDT_HIP_ANCHOR_AFTER : CRDT_HIP_ANCHOR_BEFORE, bytes),
+            anchor_of(end, expand & EXPAND_END ? CRDT_HIP_ANCHOR_BEFORE : CRDT_HIP_ANCHOR_AFTER, bytes),
+            key, value, flags, sv);
+    }
+    Spans spans_of(bool bytes) const {
+        flush();
+        return spans_get(
+            [&](const Format* f, size_t n, crdt_hip_span* out, size_t cap, size_t* on,
+                crdt_hip_span_attr* at, size_t acap, size_t* oa, size_t* pend) {
+                return crdt_hip_replica_spans(dev_->ctx, rep_, f, n, out, cap, on, at, acap, oa, pend);
+            },
+            formats_, dev_->ctx, bytes);
+    }
+    FormatSet formats_;
     Anchor anchor_of(size_t pos, uint32_t bias, bool bytes) const {
         flush();
         const uint64_t p = pos;
@@ -407,6 +548,14 @@ public:
         return anchors_known(resolved(a), true);
     }
     AnchorAt resolve(const Anchor& a) const { return resolve_many({a})[0]; }
+    // Formats made at, and spans painted in, byte offsets.
+    uint64_t format(size_t start, size_t end, uint32_t key, uint64_t value, unsigned expand = 0) {
+        return format_op(start, end, key, value, 0, expand, true);
+    }
+    uint64_t unformat(size_t start, size_t end, uint32_t key, unsigned expand = 0) {
+        return format_op(start, end, key, 0, CRDT_HIP_FORMAT_REMOVE, expand, true);
+    }
+    Spans spans() const { return spans_of(true); }
 };
 
 }  // namespace hipmerge

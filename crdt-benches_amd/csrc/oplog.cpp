@@ -1002,6 +1002,161 @@ int OpLog::anchors_resolve(const AnchorRec* a, size_t n, AnchorPosRec* out, std:
     return CRDT_HIP_OK;
 }
 
+// ---- formats -----------------------------------------------------------------------------------
+int format_check(const FormatRec* f, size_t n, std::vector<uint32_t>& sorted, std::string& err) {
+    sorted.clear();
+    if (n > kFormatMax) {
+        err = "more than 65,536 formats";
+        return CRDT_HIP_ERANGE;
+    }
+    for (size_t k = 0; k < n; ++k) {
+        const AnchorRec ends[2] = {f[k].start, f[k].end};
+        const int rc = anchor_check_resolve(ends, 2, err);
+        if (rc) return rc;
+        if (f[k].op >= kDeltaKeyEnd) {
+            err = "format op of 2^48 or more";
+            return CRDT_HIP_EINVAL;
+        }
+        if (f[k].flags > kFormatRemove) {
+            err = "format flags are neither 0 nor REMOVE";
+            return CRDT_HIP_EINVAL;
+        }
+    }
+    sorted.resize(n);
+    for (size_t k = 0; k < n; ++k) sorted[k] = (uint32_t)k;
+    std::sort(sorted.begin(), sorted.end(), [&](uint32_t x, uint32_t y) { return f[x].op < f[y].op; });
+    for (size_t k = 1; k < n; ++k)
+        if (f[sorted[k]].op == f[sorted[k - 1]].op) {
+            sorted.clear();
+            err = "two formats with the same op";
+            return CRDT_HIP_EINVAL;
+        }
+    std::stable_sort(sorted.begin(), sorted.end(),
+                     [&](uint32_t x, uint32_t y) { return f[x].key < f[y].key; });
+    return CRDT_HIP_OK;
+}
+
+int OpLog::spans(const FormatRec* f, size_t n, std::vector<SpanRec>& out, std::vector<SpanAttrRec>& attrs,
+                 uint64_t& pending, std::string& err) const {
+    out.clear();
+    attrs.clear();
+    pending = 0;
+    std::vector<uint32_t> by;  // the formats by (key, op)
+    const int rc = format_check(f, n, by, err);
+    if (rc || n == 0) return rc;
+    std::vector<uint32_t> order;
+    err = document_order(order);
+    if (!err.empty()) return CRDT_HIP_EBADLOG;
+    const uint32_t N = size();
+    // the distinct identities the anchors name, sorted, and the rank of the slot that holds each
+    // (0: none; of two slots of a malformed log that share an identity, the lower)
+    std::vector<uint64_t> want;
+    want.reserve(2 * n);
+    for (size_t k = 0; k < n; ++k) {
+        if (f[k].start.id != kAnchorEdge) want.push_back(f[k].start.id);
+        if (f[k].end.id != kAnchorEdge) want.push_back(f[k].end.id);
+    }
+    std::sort(want.begin(), want.end());
+    want.erase(std::unique(want.begin(), want.end()), want.end());
+    std::vector<uint32_t> rank_of(want.size(), 0u);
+    if (!want.empty()) {
+        std::vector<uint32_t> rk(N + 1ull, 0u);  // slot -> rank
+        for (uint32_t k = 0; k < N; ++k) rk[order[k]] = k + 1;
+        for (uint32_t id = 1; id <= N; ++id) {
+            const uint64_t ident = ((uint64_t)lamport[id - 1] << 16) | agent[id - 1];
+            const auto it = std::lower_bound(want.begin(), want.end(), ident);
+            if (it != want.end() && *it == ident && !rank_of[it - want.begin()]) rank_of[it - want.begin()] = rk[id];
+        }
+    }
+    // per format its two gaps (a format that covers nothing: 1, 0), and the gaps that bound a range
+    auto gap = [&](const AnchorRec& a, uint32_t& g) {
+        if (a.id == kAnchorEdge) {
+            g = a.bias == kAnchorAfter ? 0u : N;
+            return true;
+        }
+        const uint32_t r = rank_of[std::lower_bound(want.begin(), want.end(), a.id) - want.begin()];
+        g = a.bias == kAnchorAfter ? r : r - 1;
+        return r != 0;
+    };
+    std::vector<uint32_t> gs(n), ge(n), bound;
+    for (size_t k = 0; k < n; ++k) {
+        uint32_t s = 0, e = 0;
+        const bool ks = gap(f[k].start, s), ke = gap(f[k].end, e);
+        if (!ks || !ke) ++pending;
+        if (ks && ke && s < e) {
+            gs[k] = s;
+            ge[k] = e;
+            bound.push_back(s);
+            bound.push_back(e);
+        } else {
+            gs[k] = 1;
+            ge[k] = 0;
+        }
+    }
+    std::sort(bound.begin(), bound.end());
+    bound.erase(std::unique(bound.begin(), bound.end()), bound.end());
+    if (bound.size() < 2) return CRDT_HIP_OK;
+    // the visible codepoints and bytes at the ranks up to each boundary
+    std::vector<uint64_t> vis(bound.size()), visb(bound.size());
+    {
+        uint64_t v = 0, vb = 0;
+        size_t j = 0;
+        for (uint32_t k = 0; k <= N && j < bound.size(); ++k) {  // k: a gap, right after rank k
+            if (k && !deleted[order[k - 1] - 1]) {
+                ++v;
+                vb += utf8_len_cp(cp[order[k - 1] - 1]);
+            }
+            if (bound[j] == k) {
+                vis[j] = v;
+                visb[j] = vb;
+                ++j;
+            }
+        }
+    }
+    // per segment between two boundaries that holds a visible item: its attribute set, compared
+    // with the set of the segment with a visible item before it
+    std::vector<SpanRec> sp;
+    std::vector<SpanAttrRec> at, cur;
+    bool open = false;  // the previous segment with a visible item had a set, which ends sp.back()
+    for (size_t j = 0; j + 1 < bound.size(); ++j) {
+        if (vis[j + 1] == vis[j]) continue;
+        const uint32_t lo = bound[j], hi = bound[j + 1];
+        cur.clear();
+        for (size_t i = 0; i < n;) {
+            const uint32_t key = f[by[i]].key;
+            const FormatRec* win = nullptr;
+            for (; i < n && f[by[i]].key == key; ++i)
+                if (gs[by[i]] <= lo && hi <= ge[by[i]]) win = &f[by[i]];
+            if (win && !(win->flags & kFormatRemove)) cur.push_back(SpanAttrRec{win->value, key, 0u});
+        }
+        if (cur.empty()) {
+            open = false;
+            continue;
+        }
+        bool same = open && sp.back().attr_n == cur.size();
+        for (size_t q = 0; same && q < cur.size(); ++q) {
+            const SpanAttrRec& p = at[sp.back().attr_off + q];
+            same = p.key == cur[q].key && p.value == cur[q].value;
+        }
+        if (same) {
+            sp.back().len = vis[j + 1] - sp.back().pos;
+            sp.back().len_bytes = visb[j + 1] - sp.back().pos_bytes;
+            continue;
+        }
+        if (at.size() + cur.size() >= (1ull << 32)) {
+            err = "2^32 or more span attributes";
+            return CRDT_HIP_ERANGE;
+        }
+        sp.push_back(SpanRec{vis[j], visb[j], vis[j + 1] - vis[j], visb[j + 1] - visb[j],
+                             (uint32_t)at.size(), (uint32_t)cur.size()});
+        at.insert(at.end(), cur.begin(), cur.end());
+        open = true;
+    }
+    out.swap(sp);
+    attrs.swap(at);
+    return CRDT_HIP_OK;
+}
+
 // ---- local edits as positional patches ---------------------------------------------------------
 // The argument-only checks of a patch array, in codepoints or (BYTES) in UTF-8 bytes: `visible`
 // and the non-touching rule are in the unit of pos and del.  emit(old position, del, first

@@ -154,6 +154,30 @@ int anchor_check_at(const uint64_t* pos, const uint8_t* bias, size_t n, uint64_t
                     std::string& err);
 int anchor_check_resolve(const AnchorRec* a, size_t n, std::string& err);
 
+// Formats (crdt_hip.h, "formats"; the device twin is format.hip): attribute ranges between two
+// anchors, flattened into spans.  Layouts of crdt_hip_format, crdt_hip_span, crdt_hip_span_attr.
+constexpr uint32_t kFormatRemove = 1;
+constexpr size_t kFormatMax = 65536;  // formats of one call
+struct FormatRec {
+    AnchorRec start, end;
+    uint64_t op, value;
+    uint32_t key, flags;
+};
+struct SpanRec {
+    uint64_t pos, pos_bytes, len, len_bytes;
+    uint32_t attr_off, attr_n;
+};
+struct SpanAttrRec {
+    uint64_t value;
+    uint32_t key, pad;
+};
+// The checks of a spans call that need no document, shared by the host and the device path: more
+// than kFormatMax formats (ERANGE); then per format, in array order, a malformed start or end
+// anchor (anchor_check_resolve), an op of 2^48 or more, flags other than 0 or REMOVE (EINVAL);
+// then, when every format passed, two formats with one op (EINVAL).  On success `sorted` holds the
+// indices 0..n-1 ordered by (key, op): within a key the last format that covers an item wins it.
+int format_check(const FormatRec* f, size_t n, std::vector<uint32_t>& sorted, std::string& err);
+
 class OpLog {
 public:
     // ---- SoA (index k holds item id k+1) ----
@@ -259,6 +283,14 @@ public:
     int anchors_at(const uint64_t* pos, const uint8_t* bias, size_t n, bool bytes, AnchorRec* out,
                    std::string& err) const;
     int anchors_resolve(const AnchorRec* a, size_t n, AnchorPosRec* out, std::string& err) const;
+    // Formats (crdt_hip.h, "formats"): attribute ranges on anchors -> the non-overlapping spans of
+    // the visible document with their attribute sets, and the formats whose anchors name an item
+    // the log does not hold.  The definition the device path (format.hip) is held to: the order
+    // comes from document_order per call, O(items + segments * formats); the positional index is
+    // neither read nor touched.  EINVAL, ERANGE as format_check, EBADLOG for a malformed log,
+    // ERANGE for 2^32 or more attributes.
+    int spans(const FormatRec* f, size_t n, std::vector<SpanRec>& out, std::vector<SpanAttrRec>& attrs,
+              uint64_t& pending, std::string& err) const;
     // Every item id in document order, tombstones included (RGA pre-order or Fugue in-order): the
     // sibling sort and walk that rebuild_index / rebuild_index_fugue build their index from.
     std::string document_order(std::vector<uint32_t>& order) const;

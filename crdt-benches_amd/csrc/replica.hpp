@@ -295,6 +295,26 @@ int replica_anchors_at(Engine& E, Replica& r, const uint64_t* pos, const uint8_t
 int replica_anchors_resolve(Engine& E, Replica& r, const AnchorRec* a, size_t n, AnchorPosRec* out,
                             AnchorStats* stats = nullptr);
 
+// Formats (format.hip; semantics in crdt_hip.h, host twin OpLog::spans).
+struct FormatStats {  // what the last device spans call observed (crdt_hip_format_stats)
+    uint64_t formats = 0;    // formats of the call
+    uint64_t pending = 0;    // those with an anchor whose identity the replica does not hold
+    uint64_t segments = 0;   // segments between two named gaps, before equal neighbours merge
+    uint64_t spans = 0;      // spans found
+    uint64_t ranks = 0;      // ranks of the document order streamed (the items held)
+    uint64_t device_ns = 0;  // summed device time of the call's kernels (HIP events)
+};
+struct FormatRec;
+struct SpanRec;
+struct SpanAttrRec;
+// Settles a pending decode, checks the arguments on the host (format_check), brings r.inc up to
+// date as replica_merge_inc does and waits twice: for the sizes, then for the result.  *out_n /
+// *out_attrs / *pending are written by a call that succeeds, the first two also with ESPACE (out
+// or attrs null or short, before the write pass); out and attrs only by a call that succeeds.
+int replica_spans(Engine& E, Replica& r, const FormatRec* f, size_t n, SpanRec* out, size_t cap,
+                  size_t* out_n, SpanAttrRec* attrs, size_t attr_cap, size_t* out_attrs,
+                  size_t* pending, FormatStats* stats = nullptr);
+
 // Incremental merge (incr.hip): the merged text (may be null), its UTF-8 bytes and codepoints;
 // *path = 1 when only the items appended since the previous merge_inc were ranked, 0 for a
 // full merge (the first call, a concurrent update, more than kIncMax new items, Fugue).

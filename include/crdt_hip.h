@@ -39,6 +39,10 @@
  *   cursors; no trait of the bench)
  *                        -> crdt_hip_oplog_anchors_at / _anchors_resolve, or on the device
  *                           crdt_hip_replica_anchors_at / _anchors_resolve ("anchors")
+ *   attribute ranges that converge (Peritext, yrs' Text::format, automerge's marks; no trait of
+ *   the bench)
+ *                        -> crdt_hip_oplog_spans, or on the device crdt_hip_replica_spans
+ *                           ("formats")
  *
  * Conventions
  *   - Every function returns int status: 0 = ok, < 0 = error (CRDT_HIP_E*).  Nothing throws or
@@ -590,6 +594,92 @@ int crdt_hip_replica_anchors_resolve(crdt_hip_ctx* ctx, crdt_hip_replica* r, con
  * is not included). */
 int crdt_hip_anchor_stats(const crdt_hip_ctx* ctx, uint64_t* anchors, uint64_t* unknown,
                           uint64_t* ranks, uint64_t* device_ns);
+
+/* ---- formats: rich-text attribute ranges on anchors, flattened into spans ------------------------
+ * Bold, a colour, a link: an attribute over a range of the text that must keep covering the same
+ * characters while every peer edits, and that converges when peers set and clear it concurrently
+ * (Peritext, yrs' Text::format, automerge's marks).  "Mark" already means a version here
+ * (crdt_hip_mark), so the ops are called formats and the result spans.  A format is a range
+ * between two anchors with a key, a value and the identity of the op that made it.  Formats are
+ * not stored in a log or a replica and travel in no update, delta or join: like anchors they are
+ * plain bytes (56 each) that the caller ships and unions itself, by `op`.
+ *
+ * Gaps and coverage.  Everything is defined over the document order of all items held, tombstones
+ * included, at ranks 1..N (RGA pre-order or Fugue in-order, as for anchors and patches_since).
+ * Gap g (0..N) lies right after the item of rank g: EDGE / AFTER is gap 0, EDGE / BEFORE gap N,
+ * item x with AFTER gap rank(x), with BEFORE gap rank(x) - 1.  Format f covers the item of rank k
+ * iff gap(f.start) < k <= gap(f.end).  Tombstones play no part in coverage, so two logs that hold
+ * the same items agree on it, whatever their slot numbering and whatever was deleted where.  A
+ * format with gap(start) >= gap(end) covers nothing, which is no error.  A format with an anchor
+ * whose identity the log does not hold is pending: it covers nothing and is counted in *pending,
+ * and the caller asks again after the next sync, as for UNKNOWN anchors.
+ * The biases are the expansion rule: an end AFTER the last character does not take text typed at
+ * the end, an end BEFORE the next character does; mirrored at the start.
+ *
+ * Attributes and spans.  For a visible item and a key K, of the formats of key K that are not
+ * pending and cover it, the one with the largest `op` wins.  If it is a REMOVE, or there is none,
+ * the item does not have K; otherwise it has (K, value).  An item's attribute set is these pairs,
+ * ascending by key.  A span is a maximal run of consecutive items of the visible document whose
+ * sets are equal, key for key and value for value, and not empty: tombstones between two visible
+ * items do not break a run, a visible item with an empty set does.  Spans come out ascending in
+ * pos and never overlap; their pieces of `attrs` are contiguous, attr_off ascends, and each span's
+ * attributes ascend by key.
+ *
+ * Everything is checked before any output is written: on an error `out`, `attrs` and the counts
+ * are untouched and nothing in the log or the replica changes.  The per-format checks run in array
+ * order, the duplicate check once they all passed:
+ *   CRDT_HIP_ERANGE  more than 65,536 formats
+ *   CRDT_HIP_EINVAL  a malformed start or end anchor (as *_anchors_resolve); op >= 2^48; flags
+ *                    other than 0 or REMOVE; two formats with the same op (the caller's union by op
+ *                    removes duplicates); a replica of another context
+ *   CRDT_HIP_ESPACE  `out` or `attrs` NULL or short: *out_n and *out_attrs are set to the need
+ *   CRDT_HIP_EBADLOG a malformed log (host); a kept order that disagrees with the replica (device)
+ * n == 0 is ok and gives no span; an empty log gives no span and every format on an item identity
+ * is pending.
+ *
+ * The host call is the definition, not a product path: the order comes from the log itself per
+ * call, O(items + work over the formats), and the resolver index is neither read nor disturbed.
+ * The device call is the product, with byte-identical spans, attrs and pending count.  It settles a
+ * pending decode and brings the kept document order up to date as the anchors calls do (so a call
+ * leaves the replica as a merge_inc would), makes no host copy of the replica's columns, changes
+ * no log contents and waits for the host twice (the sizes, then the result).  It counts the
+ * visible codepoints and bytes per tile of 4,096 ranks, finds the anchors' items through a hash
+ * table probed by every key, marks the gaps the formats name in a bit plane over the ranks and
+ * compacts it into the sorted boundaries, takes each boundary's visible prefix (a wave each), and
+ * per segment between two boundaries (a thread each) walks the formats, sorted by (key, op) on the
+ * host, for the segment's attribute set; equal neighbours are merged by head flags and a scan.
+ * Known cost: a call streams every rank and every key once, however few the formats; the
+ * attribute pass is O(segments * formats); after a join or a delta it first pays the full
+ * ORDER-mode rebuild. */
+enum { CRDT_HIP_FORMAT_REMOVE = 1 };
+typedef struct {
+    crdt_hip_anchor start, end;  /* the two gaps the range lies between */
+    uint64_t op;     /* identity of this format op: lamport << 16 | agent, below 2^48 */
+    uint64_t value;  /* opaque payload (a colour, 1 for bold, an index into the caller's table) */
+    uint32_t key;    /* attribute name, opaque */
+    uint32_t flags;  /* 0, or CRDT_HIP_FORMAT_REMOVE (value is ignored) */
+} crdt_hip_format;                      /* 56 bytes */
+typedef struct {
+    uint64_t pos, pos_bytes;   /* visible codepoints / UTF-8 bytes before the span */
+    uint64_t len, len_bytes;   /* visible codepoints / UTF-8 bytes of the span, len >= 1 */
+    uint32_t attr_off, attr_n; /* its attributes: attrs[attr_off, +attr_n), attr_n >= 1 */
+} crdt_hip_span;                        /* 40 bytes */
+typedef struct { uint64_t value; uint32_t key; uint32_t pad; } crdt_hip_span_attr;  /* 16 bytes */
+/* f may be NULL when n == 0; out_n, out_attrs and pending must not be NULL. */
+int crdt_hip_oplog_spans(crdt_hip_oplog* log, const crdt_hip_format* f, size_t n,
+                         crdt_hip_span* out, size_t cap, size_t* out_n,
+                         crdt_hip_span_attr* attrs, size_t attr_cap, size_t* out_attrs,
+                         size_t* pending);
+int crdt_hip_replica_spans(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_format* f,
+                           size_t n, crdt_hip_span* out, size_t cap, size_t* out_n,
+                           crdt_hip_span_attr* attrs, size_t attr_cap, size_t* out_attrs,
+                           size_t* pending);
+/* What the context's last device spans call observed (each may be NULL): formats of the call,
+ * those pending, segments between two named gaps before equal neighbours were merged, spans,
+ * ranks of the document order streamed (the items held), and the summed device time of the call's
+ * own kernels in ns (HIP events; the order update is not included). */
+int crdt_hip_format_stats(const crdt_hip_ctx* ctx, uint64_t* formats, uint64_t* pending,
+                          uint64_t* segments, uint64_t* spans, uint64_t* ranks, uint64_t* device_ns);
 
 /* ---- trace loader (crdt-testdata load_testing_data / chars_to_bytes, main.rs:19-23) ---------- */
 int crdt_hip_trace_load(const char* path, crdt_hip_trace** out);
