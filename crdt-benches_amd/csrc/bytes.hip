@@ -96,18 +96,6 @@ __global__ __launch_bounds__(kOrdTop) void k_bytes_top(BytesArgs a) {
     }
 }
 
-// The last patch whose old byte position is at most b (np: none).
-__device__ __forceinline__ uint32_t bytes_find(const BytePatch* tab, uint32_t np, uint64_t b) {
-    if (np == 0 || tab[0].old_pos_b > b) return np;
-    uint32_t lo = 0, hi = np;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (tab[mid].old_pos_b <= b) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(kOrdT) void k_bytes_translate(BytesArgs a) {
     __shared__ uint32_t lds[kOrdW];
     if (blockIdx.x >= a.ntiles) return;
@@ -131,7 +119,7 @@ __global__ __launch_bounds__(kOrdT) void k_bytes_translate(BytesArgs a) {
             ++v;
             b += w[j];
         }
-        const uint32_t k = bytes_find(a.btab, a.np, b);
+        const uint32_t k = last_at_most(a.np, b, [&](uint32_t i) { return a.btab[i].old_pos_b; });
         if (k >= a.np) continue;
         const BytePatch e = a.btab[k];
         if (b == e.old_pos_b) a.cp_start[k] = v;
@@ -179,6 +167,19 @@ void bytes_count_enqueue(const BytesArgs& a, hipStream_t s) {
     k_bytes_init<<<grid_for(std::max<uint64_t>(a.np, B_N), kJB), kJB, 0, s>>>(a);
     k_bytes_count<<<a.ntiles, kOrdT, 0, s>>>(a);
     k_bytes_top<<<1, kOrdTop, 0, s>>>(a);
+}
+
+int bytes_count_check(Engine& E, const Replica& r, const uint64_t* c, const char* who, const char* what) {
+    if (c[B_ERR] & EB_SLOT) {
+        E.err = std::string(who) + ": the kept document order names a slot that is no item";
+        return CRDT_HIP_EBADLOG;
+    }
+    if (c[B_VIS] != r.vis_cp || c[B_VISB] != r.vis_bytes) {
+        E.err = std::string(who) + ": the visible " + what +
+                " of the kept order disagree with the replica's counters";
+        return CRDT_HIP_EBADLOG;
+    }
+    return CRDT_HIP_OK;
 }
 
 void bytes_translate_enqueue(const BytesArgs& a, hipStream_t s) {

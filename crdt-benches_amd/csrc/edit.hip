@@ -165,18 +165,6 @@ __global__ __launch_bounds__(kOrdTop) void k_edit_top(EditArgs a) {
     if (threadIdx.x == 0) a.ctl[E_VIS] = c;
 }
 
-// The last patch whose old position is at most v (np: none).
-__device__ __forceinline__ uint32_t edit_find(const EditPatch* tab, uint32_t np, uint32_t v) {
-    if (np == 0 || tab[0].old_pos > v) return np;
-    uint32_t lo = 0, hi = np;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (tab[mid].old_pos <= v) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(kOrdT) void k_edit_resolve(EditArgs a) {
     __shared__ uint32_t lds[kOrdW];
     if (blockIdx.x >= a.ntiles) return;
@@ -197,7 +185,7 @@ __global__ __launch_bounds__(kOrdT) void k_edit_resolve(EditArgs a) {
         const uint64_t rank = k0 + j;
         if (!vis[j] && rank != 0) continue;
         if (vis[j]) ++v;  // this item's visible rank (the document start: 0)
-        const uint32_t k = edit_find(a.tab, a.np, v);
+        const uint32_t k = last_at_most(a.np, v, [&](uint32_t i) { return a.tab[i].old_pos; });
         if (k >= a.np) continue;
         const EditPatch e = a.tab[k];
         if (e.old_pos == v) {
@@ -475,16 +463,9 @@ int replica_apply_patches_bytes(Engine& E, Replica& r, const PatchRec* p, size_t
     CallScratch sc(s);
     HIPTRY(E, sc.counters(E_N + B_N), "hipMalloc edit counters");
     BytesArgs b{};
-    b.seq = a.seq;
-    b.cp = r.logs.cp;
-    b.n = r.n;
-    b.ntiles = a.ntiles;
+    HIPTRY(E, bytes_count_args(b, sc, r, a.seq, a.ntiles, sc.ctl + E_N), "hipMalloc byte tiles");
     b.np = (uint32_t)np;
-    b.ctl = sc.ctl + E_N;
     BytePatch* btab = nullptr;
-    HIPTRY(E, sc.alloc(&b.tcount, (uint64_t)b.ntiles), "hipMalloc byte tiles");
-    HIPTRY(E, sc.alloc(&b.tbytes, (uint64_t)b.ntiles), "hipMalloc byte tiles");
-    HIPTRY(E, sc.alloc(&b.tbpre, (uint64_t)b.ntiles), "hipMalloc byte tiles");
     HIPTRY(E, sc.alloc(&btab, np), "hipMalloc byte patches");
     HIPTRY(E, sc.alloc(&b.cp_start, np), "hipMalloc byte patches");
     HIPTRY(E, sc.alloc(&b.cp_end, np), "hipMalloc byte patches");
@@ -500,15 +481,11 @@ int replica_apply_patches_bytes(Engine& E, Replica& r, const PatchRec* p, size_t
     HIPTRY(E, hipStreamSynchronize(s), "byte translation sync");  // the wait the byte form adds
     sc.time_add();
     const uint64_t* c = sc.hctl + E_N;
-    if (c[B_ERR]) {
-        E.err = c[B_ERR] & EB_SLOT ? "edit: the kept document order names a slot that is no item"
-                                   : "edit: a patch ends before it starts";
+    if (c[B_ERR] == EB_TABLE) {  // (with EB_SLOT too, the check below names the slot first)
+        E.err = "edit: a patch ends before it starts";
         return CRDT_HIP_EBADLOG;
     }
-    if (c[B_VIS] != r.vis_cp || c[B_VISB] != r.vis_bytes) {
-        E.err = "edit: the visible bytes of the kept order disagree with the replica's counters";
-        return CRDT_HIP_EBADLOG;
-    }
+    if ((rc = bytes_count_check(E, r, c, "edit", "bytes"))) return rc;
     if (c[B_STARTS] < np || c[B_ENDS] < np) {
         E.err = "patch boundary inside a codepoint";
         return CRDT_HIP_EINVAL;

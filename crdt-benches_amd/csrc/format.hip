@@ -13,19 +13,18 @@
 //
 //   k_fmt_init      counters; the identity table and the bit plane cleared; the 2n anchor ids copied
 //                   into a contiguous column (start of format i at 2i, its end at 2i + 1)
-//   k_fmt_insert    the distinct identities into an open-addressing table of at least twice as many
-//                   entries as anchors (as k_anchor_insert)
-//   k_fmt_probe     a grid-stride pass over the key column: every item looks its identity up and, on
-//                   a hit, records its slot for the entry (atomicMin, as k_anchor_probe)
-//   k_fmt_gaps      a thread per format: slot -> rank from the kept inverse order (checked against n
-//                   and seq[rank] == slot), the two gaps, the pending flag; a format that covers
-//                   something sets its two gaps in a bit plane over the gaps 0..n (atomicOr)
+//   k_locate_insert (locate.hpp) the distinct identities into an open-addressing table of at least
+//                   twice as many entries as anchors
+//   k_locate_probe  (locate.hpp) a grid-stride pass over the key column: every item looks its
+//                   identity up and, on a hit, records its slot for the entry
+//   k_fmt_gaps      a thread per format: slot -> rank from the kept inverse order (locate_rank), the
+//                   two gaps, the pending flag; a format that covers something sets its two gaps in a
+//                   bit plane over the gaps 0..n (atomicOr)
 //   k_fmt_bcount    a wave per tile of the plane (4,096 gaps, a word per lane): its set bits
 //   k_fmt_btop      one workgroup scans the tiles' counts: the boundaries B, the segments B - 1
 //   k_fmt_bcompact  a wave per tile: its set bits, in order, into the sorted boundary array
 //   k_fmt_bpos      a wave per boundary: the visible codepoints and bytes at the ranks up to its gap,
-//                   from the tile prefixes and a walk of the tile 64 ranks a step (as
-//                   k_anchor_resolve)
+//                   from the tile prefixes and a walk of the tile 64 ranks a step (view_walk)
 //   k_fmt_live      one workgroup: the segments (boundary j, boundary j + 1] that hold a visible item,
 //                   compacted in order (a scan); the others are dropped
 //   k_fmt_count     a thread per such segment: one walk over the formats, the index the same in every
@@ -38,9 +37,9 @@
 //   k_fmt_close     a thread per segment that ends a run (its successor is a head, has an empty set,
 //                   or does not exist): the span's len and len_bytes from the boundary prefixes
 //
-// No atomic decides an order: a CAS claims a table entry, a min picks a slot, an OR sets a bit of
-// the plane or an error bit, one add per block counts the pending; the boundaries come out sorted
-// because the plane is compacted in rank order, not because of the order in which bits were set.
+// No atomic decides an order: locate.hpp says why for the table's CAS and the slot's min; here an
+// OR sets a bit of the plane or an error bit, one add per block counts the pending; the boundaries
+// come out sorted because the plane is compacted in rank order, not by when a bit was set.
 // Every slot, rank, tile, table, boundary and segment index is checked against n and the sizes of
 // the call before it becomes an address, and a bad one raises an F_ERR bit (EBADLOG) instead;
 // every loop is bounded (a probe by the table size, a walk by the tile or the format count, a
@@ -55,6 +54,7 @@
 
 #include "bytes.hpp"
 #include "idtab.hpp"
+#include "locate.hpp"
 #include "oplog.hpp"
 #include "order.hpp"
 #include "replica.hpp"
@@ -66,11 +66,8 @@ namespace {
 
 // device counters (u64), after the B_N of the count
 enum FCtl { F_ERR = 0, F_PENDING, F_BOUNDS, F_SEGS, F_LIVE, F_SPANS, F_ATTRS, F_N };
-// F_ERR bits
-constexpr uint64_t EF_SLOT = 1;    // the order names a slot that is no item of the replica
-constexpr uint64_t EF_RANK = 2;    // the inverse order names no rank, or not the slot's
-constexpr uint64_t EF_TABLE = 4;   // the identity table did not take an anchor
-constexpr uint64_t EF_BOUND = 8;   // a boundary, segment, span or attr index outside its array
+// F_ERR bits, after EL_SLOT, EL_RANK and EL_TABLE (locate.hpp)
+constexpr uint64_t EF_BOUND = 8;  // a boundary, segment, span or attr index outside its array
 constexpr uint64_t EF_RANGE = 16;  // 2^32 or more attributes
 
 constexpr uint32_t kFmtW = kJB / 64;      // waves per workgroup
@@ -84,22 +81,10 @@ struct FmtDev {  // a format on the device: its gaps (covers nothing: 1, 0) and 
 };
 
 struct FmtArgs {
-    const uint32_t* seq;     // rank -> slot, ranks 0..n
-    const uint32_t* rank;    // slot -> rank, slots 0..n
-    const uint8_t* cp;       // 3-byte codepoint words of slots 0..n
-    const uint64_t* key;
-    uint32_t n;              // items held
-    uint32_t ntiles;         // tiles of kOrderTile ranks (and gaps)
-    const uint32_t* tcount;  // per tile: visible items before it
-    const uint64_t* tbpre;   //   and their UTF-8 bytes
+    OrderView v;
     uint32_t nf;             // formats of the call
-    uint32_t m;              // their anchors, 2 * nf: also the capacity of every per-boundary array
     const FormatRec* fmt;    // the formats by (key, op)
-    uint64_t* ids;           // anchor ids, contiguous
-    uint32_t* tab;           // identity table: anchor indices (kEmpty: free), mask + 1 entries
-    uint32_t mask;
-    uint32_t* canon;         // per anchor: the anchor that owns its identity's entry
-    uint32_t* slot;          // per owning anchor: the slot that holds the identity (kEmpty: none)
+    IdLookup l;              // their anchors; l.m = 2 * nf: also the capacity of every per-boundary array
     FmtDev* fd;
     uint64_t* plane;         // a bit per gap, ntiles * kPlaneTile words
     uint32_t* tb;            // per tile: its boundaries, then their exclusive prefix
@@ -121,35 +106,11 @@ struct FmtArgs {
 __global__ __launch_bounds__(kJB) void k_fmt_init(FmtArgs a) {
     const uint64_t g = (uint64_t)blockIdx.x * kJB + threadIdx.x;
     if (g < (uint64_t)F_N) a.ctl[g] = 0;
-    if (g <= a.mask) a.tab[g] = kEmpty;
-    if (g < (uint64_t)a.ntiles * kPlaneTile) a.plane[g] = 0;
-    if (g < a.m) {
+    locate_clear(a.l, g);
+    if (g < (uint64_t)a.v.ntiles * kPlaneTile) a.plane[g] = 0;
+    if (g < a.l.m) {
         const FormatRec& f = a.fmt[g >> 1];
-        a.ids[g] = g & 1u ? f.end.id : f.start.id;
-        a.slot[g] = kEmpty;
-    }
-}
-
-__global__ __launch_bounds__(kJB) void k_fmt_insert(FmtArgs a) {
-    const uint64_t g = (uint64_t)blockIdx.x * kJB + threadIdx.x;
-    if (g >= a.m) return;
-    uint32_t owner = (uint32_t)g;
-    const uint64_t id = a.ids[g];
-    if (id != kAnchorEdge) {
-        bool full = false;
-        const uint32_t d = tab_insert<false>(a.tab, a.mask, a.ids, (uint32_t)g, id, full);
-        if (d != kEmpty) owner = d;
-        if (full) ctl_or(&a.ctl[F_ERR], EF_TABLE);
-    }
-    a.canon[g] = owner;
-}
-
-template <bool FUGUE>
-__global__ __launch_bounds__(kJB) void k_fmt_probe(FmtArgs a) {
-    for (uint64_t s = 1 + (uint64_t)blockIdx.x * kJB + threadIdx.x; s <= a.n;
-         s += (uint64_t)gridDim.x * kJB) {
-        const uint32_t e = tab_find<false>(a.tab, a.mask, a.ids, jident<FUGUE>(a.key[s]));
-        if (e != kEmpty && e < a.m) atomicMin(&a.slot[e], (uint32_t)s);
+        a.l.ids[g] = g & 1u ? f.end.id : f.start.id;
     }
 }
 
@@ -159,21 +120,11 @@ __device__ __forceinline__ bool fmt_gap(const FmtArgs& a, const AnchorRec& an, u
                                         uint32_t& gap, uint64_t& err) {
     gap = 0;
     if (an.id == kAnchorEdge) {
-        gap = an.bias == kAnchorAfter ? 0u : a.n;
+        gap = an.bias == kAnchorAfter ? 0u : a.v.n;
         return true;
     }
-    const uint32_t own = a.canon[idx];
-    const uint32_t s = own < a.m ? a.slot[own] : 0u;
-    if (s == kEmpty) return false;
-    if (s == 0 || s > a.n) {
-        err |= EF_TABLE;
-        return false;
-    }
-    const uint32_t rk = a.rank[s];
-    if (rk == 0 || rk > a.n || a.seq[rk] != s) {
-        err |= EF_RANK;
-        return false;
-    }
+    uint32_t s, rk;
+    if (locate_rank(a.l, a.v, idx, s, rk, err) != Loc::Found) return false;
     gap = an.bias == kAnchorAfter ? rk : rk - 1u;
     return true;
 }
@@ -207,16 +158,16 @@ __global__ __launch_bounds__(kJB) void k_fmt_gaps(FmtArgs a) {
 __global__ __launch_bounds__(kJB) void k_fmt_bcount(FmtArgs a) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t t = (uint64_t)blockIdx.x * kFmtW + (threadIdx.x >> 6);
-    if (t >= a.ntiles) return;
+    if (t >= a.v.ntiles) return;
     const uint32_t c = wave_sum((uint32_t)__popcll(a.plane[t * kPlaneTile + lane]));
     if (lane == 0) a.tb[t] = c;
 }
 
 __global__ __launch_bounds__(kOrdTop) void k_fmt_btop(FmtArgs a) {
     __shared__ uint32_t lds[kOrdTop / 64];
-    const uint64_t b = block_scan_counts<kOrdTop>(a.tb, a.ntiles, lds);
+    const uint64_t b = block_scan_counts<kOrdTop>(a.tb, a.v.ntiles, lds);
     if (threadIdx.x == 0) {
-        if (b > a.m) ctl_or(&a.ctl[F_ERR], EF_BOUND);  // (at most two gaps a format)
+        if (b > a.l.m) ctl_or(&a.ctl[F_ERR], EF_BOUND);  // (at most two gaps a format)
         a.ctl[F_BOUNDS] = b;
         a.ctl[F_SEGS] = b ? b - 1 : 0;
     }
@@ -225,7 +176,7 @@ __global__ __launch_bounds__(kOrdTop) void k_fmt_btop(FmtArgs a) {
 __global__ __launch_bounds__(kJB) void k_fmt_bcompact(FmtArgs a) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t t = (uint64_t)blockIdx.x * kFmtW + (threadIdx.x >> 6);
-    if (t >= a.ntiles) return;
+    if (t >= a.v.ntiles) return;
     uint64_t w = a.plane[t * kPlaneTile + lane];
     const uint32_t c = (uint32_t)__popcll(w);
     const uint64_t base = (uint64_t)a.tb[t] + wave_incl_scan(c) - c;
@@ -234,34 +185,21 @@ __global__ __launch_bounds__(kJB) void k_fmt_bcompact(FmtArgs a) {
         const uint32_t bit = (uint32_t)__ffsll((long long)w) - 1u;
         w &= w - 1;
         const uint64_t gap = t * kOrderTile + lane * 64u + bit;
-        if (base + q < a.m && gap <= a.n) a.bounds[base + q] = (uint32_t)gap;
+        if (base + q < a.l.m && gap <= a.v.n) a.bounds[base + q] = (uint32_t)gap;
         else err |= EF_BOUND;
     }
     ctl_or(&a.ctl[F_ERR], err);
-}
-
-// The UTF-8 length of the visible item at rank k (0: rank 0, a rank past n, a tombstone, or a slot
-// that is no item, which also raises EF_SLOT).
-__device__ __forceinline__ uint32_t fmt_len(const FmtArgs& a, uint64_t k, uint64_t& err) {
-    if (k == 0 || k > a.n) return 0;
-    const uint32_t sl = a.seq[k];
-    if (sl == 0 || sl > a.n) {
-        err |= EF_SLOT;
-        return 0;
-    }
-    const uint32_t c = cp3_get(a.cp, sl);
-    return c & kDelBit ? 0u : utf8_len(c & kDeltaCpMask);
 }
 
 // The boundaries and the segments of the call, as the earlier kernels left them, held to the
 // capacity of the arrays.
 __device__ __forceinline__ uint32_t fmt_nbounds(const FmtArgs& a) {
     const uint64_t b = a.ctl[F_BOUNDS];
-    return b < a.m ? (uint32_t)b : a.m;
+    return b < a.l.m ? (uint32_t)b : a.l.m;
 }
 __device__ __forceinline__ uint32_t fmt_nlive(const FmtArgs& a) {
     const uint64_t l = a.ctl[F_LIVE];
-    return l < a.m ? (uint32_t)l : a.m;
+    return l < a.l.m ? (uint32_t)l : a.l.m;
 }
 
 // A wave per boundary.  Everything that branches depends on the boundary alone, so a wave stays
@@ -273,19 +211,10 @@ __global__ __launch_bounds__(kJB) void k_fmt_bpos(FmtArgs a) {
     uint64_t err = 0;
     const uint32_t g = a.bounds[i];
     uint64_t pos = 0, posb = 0;
-    if (g > a.n) {
+    if (g > a.v.n) {
         err |= EF_BOUND;
-    } else {
-        const uint32_t tile = g / kOrderTile;  // (below ntiles: g <= n)
-        uint32_t cnt = 0, by = 0;
-        for (uint32_t k0 = tile * kOrderTile; k0 <= g; k0 += 64u) {
-            const uint32_t wt = k0 + lane <= g ? fmt_len(a, k0 + lane, err) : 0u;
-            cnt += (uint32_t)__popcll(__ballot(wt != 0));
-            by += wt;
-        }
-        by = wave_sum(by);  // (a tile holds at most 16 KiB)
-        pos = (uint64_t)a.tcount[tile] + cnt;
-        posb = a.tbpre[tile] + by;
+    } else {  // the ranks up to and including g, in g's own tile (below ntiles: g <= n)
+        view_walk(a.v, g / kOrderTile, g + 1u, lane, pos, posb, err);
     }
     if (lane == 0) {
         a.bpos[i] = pos;
@@ -458,9 +387,9 @@ int fmt_fail(Engine& E, uint64_t e) {
         E.err = "spans: 2^32 or more span attributes";
         return CRDT_HIP_ERANGE;
     }
-    E.err = e & EF_SLOT    ? "spans: the kept document order names a slot that is no item"
-            : e & EF_RANK  ? "spans: the kept inverse order disagrees with the order"
-            : e & EF_TABLE ? "spans: the identity table did not take every anchor"
+    E.err = e & EL_SLOT    ? "spans: the kept document order names a slot that is no item"
+            : e & EL_RANK  ? "spans: the kept inverse order disagrees with the order"
+            : e & EL_TABLE ? "spans: the identity table did not take every anchor"
                            : "spans: a boundary or a segment lies outside the call's arrays";
     return CRDT_HIP_EBADLOG;
 }
@@ -491,39 +420,29 @@ int replica_spans(Engine& E, Replica& r, const FormatRec* f, size_t n, SpanRec* 
     std::vector<FormatRec> sorted(n);  // (outlives the scratch, whose release waits for the stream)
     for (size_t k = 0; k < n; ++k) sorted[k] = f[by[k]];
     FmtArgs a{};
-    rc = replica_kept_ranks(E, r, "spans", &a.seq, &a.rank, &a.ntiles);
+    rc = replica_kept_ranks(E, r, "spans", &a.v.seq, &a.v.rank, &a.v.ntiles);
     if (rc) return rc;
     hipStream_t s = E.stream;
     CallScratch sc(s);
     HIPTRY(E, sc.counters(B_N + F_N), "hipMalloc format counters");
     BytesArgs b{};
-    b.seq = a.seq;
-    b.cp = r.logs.cp;
-    b.n = r.n;
-    b.ntiles = a.ntiles;
-    b.ctl = sc.ctl;
-    HIPTRY(E, sc.alloc(&b.tcount, (uint64_t)b.ntiles), "hipMalloc format tiles");
-    HIPTRY(E, sc.alloc(&b.tbytes, (uint64_t)b.ntiles), "hipMalloc format tiles");
-    HIPTRY(E, sc.alloc(&b.tbpre, (uint64_t)b.ntiles), "hipMalloc format tiles");
-    a.cp = r.logs.cp;
-    a.key = r.logs.key;
-    a.n = r.n;
-    a.tcount = b.tcount;
-    a.tbpre = b.tbpre;
+    HIPTRY(E, bytes_count_args(b, sc, r, a.v.seq, a.v.ntiles, sc.ctl), "hipMalloc format tiles");
+    a.v.cp = r.logs.cp;
+    a.v.key = r.logs.key;
+    a.v.n = r.n;
+    a.v.tcount = b.tcount;
+    a.v.tbpre = b.tbpre;
+    a.v.vis = sc.ctl + B_VIS;
     a.nf = (uint32_t)n;
-    a.m = 2u * (uint32_t)n;  // (n <= 65,536)
     a.ctl = sc.ctl + B_N;
-    const uint64_t m = a.m, tcap = pow2_at_least(2 * m), words = (uint64_t)a.ntiles * kPlaneTile;
-    a.mask = (uint32_t)(tcap - 1);
+    const uint64_t m = 2 * (uint64_t)n, words = (uint64_t)a.v.ntiles * kPlaneTile;  // (n <= 65,536)
     FormatRec* dfmt = nullptr;
     HIPTRY(E, sc.alloc(&dfmt, n), "hipMalloc formats");
-    HIPTRY(E, sc.alloc(&a.ids, m), "hipMalloc format ids");
-    HIPTRY(E, sc.alloc(&a.tab, tcap), "hipMalloc format table");
-    HIPTRY(E, sc.alloc(&a.canon, m), "hipMalloc format table");
-    HIPTRY(E, sc.alloc(&a.slot, m), "hipMalloc format slots");
+    HIPTRY(E, locate_alloc(sc, a.l, (uint32_t)m), "hipMalloc format table");
+    const uint64_t tcap = (uint64_t)a.l.mask + 1;
     HIPTRY(E, sc.alloc(&a.fd, n), "hipMalloc formats");
     HIPTRY(E, sc.alloc(&a.plane, words), "hipMalloc format plane");
-    HIPTRY(E, sc.alloc(&a.tb, (uint64_t)a.ntiles), "hipMalloc format tiles");
+    HIPTRY(E, sc.alloc(&a.tb, (uint64_t)a.v.ntiles), "hipMalloc format tiles");
     HIPTRY(E, sc.alloc(&a.bounds, m), "hipMalloc format boundaries");
     HIPTRY(E, sc.alloc(&a.bpos, m), "hipMalloc format boundaries");
     HIPTRY(E, sc.alloc(&a.bposb, m), "hipMalloc format boundaries");
@@ -538,13 +457,13 @@ int replica_spans(Engine& E, Replica& r, const FormatRec* f, size_t n, SpanRec* 
     HIPTRY(E, sc.time_begin(), "format event");
     bytes_count_enqueue(b, s);
     k_fmt_init<<<grid_for(std::max<uint64_t>(std::max<uint64_t>(tcap, words), F_N), kJB), kJB, 0, s>>>(a);
-    k_fmt_insert<<<grid_for(m, kJB), kJB, 0, s>>>(a);
-    if (r.logs.fugue) k_fmt_probe<true><<<grid_stride(r.n), kJB, 0, s>>>(a);
-    else k_fmt_probe<false><<<grid_stride(r.n), kJB, 0, s>>>(a);
+    k_locate_insert<<<grid_for(m, kJB), kJB, 0, s>>>(a.l, &a.ctl[F_ERR]);
+    if (r.logs.fugue) k_locate_probe<true><<<grid_stride(r.n), kJB, 0, s>>>(a.l, a.v.key, r.n);
+    else k_locate_probe<false><<<grid_stride(r.n), kJB, 0, s>>>(a.l, a.v.key, r.n);
     k_fmt_gaps<<<grid_for(n, kJB), kJB, 0, s>>>(a);
-    k_fmt_bcount<<<grid_for(a.ntiles, kFmtW), kJB, 0, s>>>(a);
+    k_fmt_bcount<<<grid_for(a.v.ntiles, kFmtW), kJB, 0, s>>>(a);
     k_fmt_btop<<<1, kOrdTop, 0, s>>>(a);
-    k_fmt_bcompact<<<grid_for(a.ntiles, kFmtW), kJB, 0, s>>>(a);
+    k_fmt_bcompact<<<grid_for(a.v.ntiles, kFmtW), kJB, 0, s>>>(a);
     k_fmt_bpos<<<grid_for(m, kFmtW), kJB, 0, s>>>(a);
     k_fmt_live<<<1, kOrdT, 0, s>>>(a);
     k_fmt_count<<<grid_for(m, kJB), kJB, 0, s>>>(a);
@@ -560,11 +479,7 @@ int replica_spans(Engine& E, Replica& r, const FormatRec* f, size_t n, SpanRec* 
         stats->ranks = r.n;
         stats->device_ns = sc.dev_ns;
     }
-    if (h[B_ERR]) return fmt_fail(E, EF_SLOT);
-    if (h[B_VIS] != r.vis_cp || h[B_VISB] != r.vis_bytes) {
-        E.err = "spans: the visible items of the kept order disagree with the replica's counters";
-        return CRDT_HIP_EBADLOG;
-    }
+    if ((rc = bytes_count_check(E, r, h, "spans", "items"))) return rc;
     if (h[B_N + F_ERR]) return fmt_fail(E, h[B_N + F_ERR]);
     const uint64_t nsp = h[B_N + F_SPANS], nat = h[B_N + F_ATTRS], pend = h[B_N + F_PENDING];
     if (nsp > m || nat < nsp || pend > n) return fmt_fail(E, EF_BOUND);

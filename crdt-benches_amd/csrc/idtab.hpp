@@ -1,8 +1,8 @@
-// idtab.hpp — what the kernels that name items by identity share (join.hip, delta.hip): the
-// identity of a key word, the open-addressing identity table (u32 entries claimed by atomicCAS,
-// identity equality by gathering the key column) and the ids of the items new to dst; and, for
-// patch.hip and edit.hip too, the block reductions that keep device counters to one atomic per
-// block.  Header-only, internal linkage.
+// idtab.hpp — what the kernels that name items by identity share (join.hip, delta.hip, and through
+// locate.hpp anchor.hip and format.hip): the identity of a key word, the open-addressing identity
+// table (u32 entries claimed by atomicCAS, identity equality by gathering the key column) and the
+// ids of the items new to dst; and, for patch.hip, edit.hip and bytes.hip too, the block reductions
+// that keep device counters to one atomic per block.  Header-only, internal linkage.
 #pragma once
 #include <algorithm>
 #include <cstdint>

@@ -1,7 +1,9 @@
-// order.hpp — how patch.hip and edit.hip stream the document order a replica keeps after a
-// merge_inc (IncState::seq[cur], rank -> slot, ranks 0..n, tombstones included; obtained and
+// order.hpp — how patch.hip, edit.hip and bytes.hip stream the document order a replica keeps after
+// a merge_inc (IncState::seq[cur], rank -> slot, ranks 0..n, tombstones included; obtained and
 // checked by replica_kept_order, incr.hip): a workgroup per tile of consecutive ranks, four ranks
-// per thread, and one workgroup over the tiles' aggregates.  Header-only, internal linkage.
+// per thread, and one workgroup over the tiles' aggregates.  anchor.hip and format.hip walk single
+// tiles of the same size a wave at a time (locate.hpp); incr.hip sizes the tiles.  Header-only,
+// internal linkage.
 #pragma once
 #include <cstdint>
 

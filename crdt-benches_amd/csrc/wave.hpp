@@ -93,6 +93,19 @@ __device__ __forceinline__ uint32_t utf8_len(uint32_t c) {
     return c < 0x80u ? 1u : c < 0x800u ? 2u : c < 0x10000u ? 3u : 4u;
 }
 
+// The last index in [0, n) whose key is at most v (n: none); key(i) ascends.
+template <class V, class K>
+__device__ __forceinline__ uint32_t last_at_most(uint32_t n, V v, K&& key) {
+    if (n == 0 || key(0) > v) return n;
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (key(mid) <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // ---- device memory (host side) ----
 template <class T>
 hipError_t dalloc(T** p, uint64_t count) {
