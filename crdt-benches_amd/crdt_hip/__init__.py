@@ -68,6 +68,7 @@ EXPORTS = [
     "crdt_hip_replica_anchors_at_bytes", "crdt_hip_replica_anchors_resolve",
     "crdt_hip_anchor_stats",
     "crdt_hip_oplog_spans", "crdt_hip_replica_spans", "crdt_hip_format_stats",
+    "crdt_hip_oplog_text_at", "crdt_hip_replica_text_at", "crdt_hip_text_stats",
 ]
 
 
@@ -220,6 +221,9 @@ def lib() -> C.CDLL:
         "crdt_hip_oplog_spans": (i32, [vp, vp, sz, vp, sz, P(sz), vp, sz, P(sz), P(sz)]),
         "crdt_hip_replica_spans": (i32, [vp, vp, vp, sz, vp, sz, P(sz), vp, sz, P(sz), P(sz)]),
         "crdt_hip_format_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64), P(u64), P(u64)]),
+        "crdt_hip_oplog_text_at": (i32, [vp, vp, u64, u64, u32, vp, sz, P(sz), vp]),
+        "crdt_hip_replica_text_at": (i32, [vp, vp, vp, u64, u64, u32, vp, sz, P(sz), vp]),
+        "crdt_hip_text_stats": (i32, [vp, P(u64), P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge": (i32, [vp, vp, vp, sz, P(sz), P(u64)]),
         "crdt_hip_replica_merge_len": (i32, [vp, vp, P(u64), P(u64), P(u64)]),
         "crdt_hip_replica_merge_inc": (i32, [vp, vp, vp, sz, P(sz), P(u64), P(u32)]),
@@ -421,6 +425,44 @@ def _patches_pack(patches, ins=None) -> tuple:
         parts.append(b)
         off += len(b)
     return arr, b"".join(parts)
+
+
+# Text windows (crdt_hip.h, "text windows"): a range of the document, now or at a mark.
+TEXT_END = 0xFFFFFFFFFFFFFFFF
+TEXT_BYTES = 1
+
+
+class TextInfo(C.Structure):
+    """crdt_hip_text_info: the whole version and the window, each in codepoints and UTF-8 bytes."""
+    _fields_ = [("len", C.c_uint64), ("len_bytes", C.c_uint64), ("start", C.c_uint64),
+                ("start_bytes", C.c_uint64), ("n", C.c_uint64), ("n_bytes", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _text_get(call, mark, start, end, bytes_, ctx=None, guess: int = 0, info_only: bool = False):
+    """call(mark handle, start, end, flags, out, cap, out_len, info) under the ESPACE convention ->
+    (the window's UTF-8, its info as a dict); info_only: sized with a NULL buffer, ESPACE accepted,
+    and only the info is returned.  `guess`: the first capacity to try (a device call streams the
+    replica's document order every time)."""
+    h = mark._h if mark is not None else None
+    e = TEXT_END if end is None else end
+    flags = TEXT_BYTES if bytes_ else 0
+    n, info = C.c_size_t(0), TextInfo()
+    if info_only:
+        rc = call(h, start, e, flags, None, 0, C.byref(n), C.byref(info))
+        if rc != -6:
+            _check(rc, ctx)
+        return info.as_dict()
+    buf = np.empty(guess, np.uint8)
+    rc = call(h, start, e, flags, buf.ctypes.data if buf.size else None, buf.size, C.byref(n),
+              C.byref(info))
+    if rc == -6:
+        buf = np.empty(n.value, np.uint8)
+        rc = call(h, start, e, flags, buf.ctypes.data, buf.size, C.byref(n), C.byref(info))
+    _check(rc, ctx)
+    return buf[: n.value].tobytes(), info.as_dict()
 
 
 # Anchors (crdt_hip.h, "anchors"): a place in the text named by the identity of the item next to
@@ -674,6 +716,20 @@ class OpLog:
         applied in that order, each as replace(pos, pos + del, ins), to the text at the mark they
         give the text now (crdt_hip_oplog_patches_since)."""
         return _patch_list(self.patches_since_raw(mark))
+
+    def text_at(self, mark: Mark = None, start: int = 0, end: int = None, bytes: bool = False) -> bytes:
+        """The UTF-8 of window [start, end) of the version now (`mark` None) or at `mark`, in
+        codepoints or, with `bytes`, in UTF-8 bytes; `end` None is the version's end
+        (crdt_hip_oplog_text_at).  The text at a mark is byte for byte what the log held when the
+        mark was taken."""
+        return _text_get(lambda *a: lib().crdt_hip_oplog_text_at(self._h, *a), mark, start, end,
+                         bytes, guess=1 << 12)[0]
+
+    def text_info(self, mark: Mark = None, start: int = 0, end: int = None, bytes: bool = False) -> dict:
+        """crdt_hip_text_info of that window alone: len, len_bytes, start, start_bytes, n, n_bytes
+        (a position translation between codepoints and bytes)."""
+        return _text_get(lambda *a: lib().crdt_hip_oplog_text_at(self._h, *a), mark, start, end,
+                         bytes, info_only=True)
 
     def apply_patches(self, patches, ins=None) -> tuple:
         """Local edits as a set of positional patches in the patches_since convention
@@ -965,6 +1021,14 @@ class Context:
         return {"anchors": int(a.value), "unknown": int(u.value), "ranks": int(r.value),
                 "device_ns": int(ns.value)}
 
+    def text_stats(self) -> dict:
+        """What this context's last Replica.text_at or text_info observed (crdt_hip_text_stats)."""
+        r, t, b, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().crdt_hip_text_stats(self._h, C.byref(r), C.byref(t), C.byref(b), C.byref(ns)),
+               self._h)
+        return {"ranks": int(r.value), "tiles_written": int(t.value), "bytes": int(b.value),
+                "device_ns": int(ns.value)}
+
     def format_stats(self) -> dict:
         """What this context's last Replica.spans observed (crdt_hip_format_stats)."""
         v = [C.c_uint64() for _ in range(6)]
@@ -1236,6 +1300,18 @@ class Replica:
         """OpLog.patches_since on the device (crdt_hip_replica_patches_since): the same patches.
         Leaves the replica as a merge_inc would."""
         return _patch_list(self.patches_since_raw(mark))
+
+    def text_at(self, mark: Mark = None, start: int = 0, end: int = None, bytes: bool = False) -> bytes:
+        """OpLog.text_at on the device (crdt_hip_replica_text_at): the same bytes, from kernels that
+        write only the tiles of the document order the window overlaps.  Leaves the replica as a
+        merge_inc would."""
+        return _text_get(lambda *a: lib().crdt_hip_replica_text_at(self.ctx._h, self._h, *a), mark,
+                         start, end, bytes, self.ctx._h, guess=1 << 16)[0]
+
+    def text_info(self, mark: Mark = None, start: int = 0, end: int = None, bytes: bool = False) -> dict:
+        """OpLog.text_info on the device: the count and scan alone, no write pass."""
+        return _text_get(lambda *a: lib().crdt_hip_replica_text_at(self.ctx._h, self._h, *a), mark,
+                         start, end, bytes, self.ctx._h, info_only=True)
 
     def set_agent(self, agent: int) -> None:
         """The agent id of this replica's later local edits (crdt_hip_replica_set_agent; default
@@ -1552,6 +1628,16 @@ class HipMerge(_RichText):
         finally:
             m.close()
 
+    def text_range(self, start: int, end: int = None) -> str:
+        """Window [start, end) of the document now, in the adapter's unit (OpLog.text_at): what an
+        editor paints."""
+        return self.text_at(None, start, end)
+
+    def text_at(self, mark: Mark, start: int = 0, end: int = None) -> str:
+        """The document as of `mark`, or window [start, end) of it (OpLog.text_at): history without
+        a saved copy of the text."""
+        return self.log.text_at(mark, start, end, self.EDITS_USE_BYTE_OFFSETS).decode("utf-8")
+
     def anchor_at(self, pos: int, bias: int = AFTER) -> tuple:
         """A cursor at gap `pos` as (id, bias): a place that survives every later edit and sync and
         means the same on every peer (OpLog.anchors_at)."""
@@ -1662,6 +1748,16 @@ class HipDownstream(_RichText):
             return self.patches_since(m)
         finally:
             m.close()
+
+    def text_range(self, start: int, end: int = None) -> str:
+        """HipMerge.text_range on the device: the queued updates are decoded first, and only the
+        window comes back (Replica.text_at; positions in the adapter's unit)."""
+        return self.text_at(None, start, end)
+
+    def text_at(self, mark: Mark, start: int = 0, end: int = None) -> str:
+        """HipMerge.text_at on the device: the queued updates are decoded first."""
+        self.flush()
+        return self.replica.text_at(mark, start, end, self.EDITS_USE_BYTE_OFFSETS).decode("utf-8")
 
     def anchor_at(self, pos: int, bias: int = AFTER) -> tuple:
         """HipMerge.anchor_at on the device: the queued updates are decoded first."""

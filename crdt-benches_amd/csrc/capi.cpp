@@ -37,6 +37,7 @@ struct crdt_hip_ctx {
     crdt::EditStats last_edit;    // what the last device apply_patches observed
     crdt::AnchorStats last_anchor;  // what the last device anchors_at / anchors_resolve observed
     crdt::FormatStats last_format;  // what the last device spans observed
+    crdt::TextStats last_text;      // what the last device text_at observed
 };
 namespace {
 // Names the owner of a mark: every log and replica handle gets its own, a clone included.
@@ -1194,6 +1195,47 @@ int crdt_hip_replica_patches_since_bytes(crdt_hip_ctx* ctx, crdt_hip_replica* r,
                                     ctx->eng, r->r, m->dev, reinterpret_cast<crdt::PatchRec*>(out), cap,
                                     out_n, ins, ins_cap, out_ins, &ctx->last_patch));
     });
+}
+// ---- text windows: a range of the document, now or at a mark ---------------------------------------
+static_assert(sizeof(crdt_hip_text_info) == sizeof(crdt::TextInfo) && sizeof(crdt_hip_text_info) == 48 &&
+                  CRDT_HIP_TEXT_END == crdt::kTextEnd && CRDT_HIP_TEXT_BYTES == crdt::kTextBytes,
+              "text info layout");
+int crdt_hip_oplog_text_at(crdt_hip_oplog* log, const crdt_hip_mark* m, uint64_t start, uint64_t end,
+                           uint32_t flags, uint8_t* out, size_t cap, size_t* out_len,
+                           crdt_hip_text_info* info) {
+    if (!log) return set_err(nullptr, CRDT_HIP_EINVAL, "null argument");
+    if (m && m->ctx) return set_err(nullptr, CRDT_HIP_EINVAL, "a replica's mark passed to a log");
+    if (m && m->owner != log->uid) return set_err(nullptr, CRDT_HIP_EINVAL, "the mark belongs to another log");
+    return guard(nullptr, [&] {
+        std::string e;
+        const int rc = log->log.text_at(m ? &m->host : nullptr, start, end, flags, out, cap, out_len,
+                                        reinterpret_cast<crdt::TextInfo*>(info), e);
+        return rc ? set_err(nullptr, rc, e) : 0;
+    });
+}
+int crdt_hip_replica_text_at(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_mark* m,
+                             uint64_t start, uint64_t end, uint32_t flags, uint8_t* out, size_t cap,
+                             size_t* out_len, crdt_hip_text_info* info) {
+    if (!ctx || !r) return set_err(ctx, CRDT_HIP_EINVAL, "null argument");
+    if (r->ctx != ctx) return set_err(ctx, CRDT_HIP_EINVAL, "replica belongs to another context");
+    if (m && !m->ctx) return set_err(ctx, CRDT_HIP_EINVAL, "a log's mark passed to a replica");
+    if (m && (m->ctx != ctx || m->owner != r->uid))
+        return set_err(ctx, CRDT_HIP_EINVAL, "the mark belongs to another replica");
+    return guard(ctx, [&] {
+        return from_engine(ctx, crdt::replica_text_at(ctx->eng, r->r, m ? &m->dev : nullptr, start, end,
+                                                      flags, out, cap, out_len,
+                                                      reinterpret_cast<crdt::TextInfo*>(info),
+                                                      &ctx->last_text));
+    });
+}
+int crdt_hip_text_stats(const crdt_hip_ctx* ctx, uint64_t* ranks, uint64_t* tiles_written,
+                        uint64_t* bytes, uint64_t* device_ns) {
+    if (!ctx) return set_err(nullptr, CRDT_HIP_EINVAL, "null context");
+    if (ranks) *ranks = ctx->last_text.ranks;
+    if (tiles_written) *tiles_written = ctx->last_text.tiles_written;
+    if (bytes) *bytes = ctx->last_text.bytes;
+    if (device_ns) *device_ns = ctx->last_text.device_ns;
+    return 0;
 }
 // ---- anchors: cursor and selection positions that survive sync --------------------------------------
 static_assert(sizeof(crdt_hip_anchor) == sizeof(crdt::AnchorRec) && sizeof(crdt_hip_anchor) == 16 &&

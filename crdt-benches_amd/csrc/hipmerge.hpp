@@ -76,6 +76,25 @@ std::vector<Patch> patches_get(Call&& call, crdt_hip_ctx* ctx, size_t cap0, size
     return out;
 }
 
+// call(start, end, flags, out, cap, out_len, info) under the ESPACE convention -> the window's UTF-8
+// (crdt_hip.h, "text windows").  cap0: the first capacity to try (a device call streams the
+// document order every time); end == npos is the version's end.
+template <class Call>
+std::string text_get(Call&& call, crdt_hip_ctx* ctx, size_t start, size_t end, bool bytes, size_t cap0) {
+    const uint64_t e = end == std::string::npos ? CRDT_HIP_TEXT_END : (uint64_t)end;
+    const uint32_t flags = bytes ? CRDT_HIP_TEXT_BYTES : 0u;
+    std::string out(cap0, '\0');
+    size_t n = 0;
+    int rc = call(start, e, flags, reinterpret_cast<uint8_t*>(out.data()), out.size(), &n, nullptr);
+    if (rc == CRDT_HIP_ESPACE) {
+        out.resize(n);
+        rc = call(start, e, flags, reinterpret_cast<uint8_t*>(out.data()), out.size(), &n, nullptr);
+    }
+    check(rc, ctx, "text_at");
+    out.resize(n);
+    return out;
+}
+
 // A cursor, a selection end: a place in the text that survives every edit and sync and means the
 // same on every peer (crdt_hip_anchor; 16 plain bytes, shipped as they are).
 using Anchor = crdt_hip_anchor;
@@ -268,6 +287,14 @@ public:
             },
             nullptr, 0, 0);
     }
+    // Window [start, end) of the document now (what an editor paints), and the document as of a
+    // mark, or a window of it: byte for byte what this log held when the mark was taken.
+    std::string text_range(size_t start, size_t end = std::string::npos) const {
+        return text_window(nullptr, start, end);
+    }
+    std::string text_at(const Mark& m, size_t start = 0, size_t end = std::string::npos) const {
+        return text_window(m.get(), start, end);
+    }
     // The anchor of gap `pos` (bias: CRDT_HIP_ANCHOR_AFTER sticks to the item before the gap,
     // BEFORE to the one after it), and where anchors made here or on any peer lie now.
     Anchor anchor_at(size_t pos, uint32_t bias = CRDT_HIP_ANCHOR_AFTER) const {
@@ -318,6 +345,14 @@ private:
         return formats_.add(anchor_at(start, expand & EXPAND_START ? CRDT_HIP_ANCHOR_AFTER : CRDT_HIP_ANCHOR_BEFORE),
                             anchor_at(end, expand & EXPAND_END ? CRDT_HIP_ANCHOR_BEFORE : CRDT_HIP_ANCHOR_AFTER),
                             key, value, flags, sv);
+    }
+    std::string text_window(const crdt_hip_mark* m, size_t start, size_t end) const {
+        return text_get(
+            [&](uint64_t s, uint64_t e, uint32_t flags, uint8_t* out, size_t cap, size_t* n,
+                crdt_hip_text_info* info) {
+                return crdt_hip_oplog_text_at(log_.get(), m, s, e, flags, out, cap, n, info);
+            },
+            nullptr, start, end, false, 1 << 12);
     }
     FormatSet formats_;
     struct Free {
@@ -421,6 +456,14 @@ public:
             },
             dev_->ctx, 4096, 1 << 16);
     }
+    // HipMerge::text_range / text_at on the device (the queued updates are decoded first): only the
+    // window comes back, from kernels that write the tiles of the kept order it overlaps.
+    std::string text_range(size_t start, size_t end = std::string::npos) const {
+        return text_window(nullptr, start, end, false);
+    }
+    std::string text_at(const Mark& m, size_t start = 0, size_t end = std::string::npos) const {
+        return text_window(m.get(), start, end, false);
+    }
     // HipMerge::anchor_at / resolve / resolve_many on the device (the queued updates are decoded
     // first): resolved in HIP kernels against the replica's kept document order.
     Anchor anchor_at(size_t pos, uint32_t bias = CRDT_HIP_ANCHOR_AFTER) const {
@@ -470,6 +513,15 @@ protected:
             formats_, dev_->ctx, bytes);
     }
     FormatSet formats_;
+    std::string text_window(const crdt_hip_mark* m, size_t start, size_t end, bool bytes) const {
+        flush();
+        return text_get(
+            [&](uint64_t s, uint64_t e, uint32_t flags, uint8_t* out, size_t cap, size_t* n,
+                crdt_hip_text_info* info) {
+                return crdt_hip_replica_text_at(dev_->ctx, rep_, m, s, e, flags, out, cap, n, info);
+            },
+            dev_->ctx, start, end, bytes, 1 << 16);
+    }
     Anchor anchor_of(size_t pos, uint32_t bias, bool bytes) const {
         flush();
         const uint64_t p = pos;
@@ -539,6 +591,13 @@ public:
                                                             ins, icap, nb);
             },
             dev_->ctx, 4096, 1 << 16);
+    }
+    // Windows in byte offsets (a boundary inside a codepoint is an error).
+    std::string text_range(size_t start, size_t end = std::string::npos) const {
+        return text_window(nullptr, start, end, true);
+    }
+    std::string text_at(const Mark& m, size_t start = 0, size_t end = std::string::npos) const {
+        return text_window(m.get(), start, end, true);
     }
     // Anchors taken at, and resolved to, byte offsets (one inside a codepoint is an error).
     Anchor anchor_at(size_t pos, uint32_t bias = CRDT_HIP_ANCHOR_AFTER) const {

@@ -858,6 +858,105 @@ int OpLog::patches_walk(const LogMark& m, bool bytes, std::vector<PatchRec>& out
     return CRDT_HIP_OK;
 }
 
+// ---- text windows ------------------------------------------------------------------------------
+int text_check(uint64_t start, uint64_t end, uint32_t flags, const size_t* out_len, std::string& err) {
+    if (flags & ~kTextBytes) {
+        err = "text flags are neither 0 nor BYTES";
+        return CRDT_HIP_EINVAL;
+    }
+    if (!out_len) {
+        err = "null out_len";
+        return CRDT_HIP_EINVAL;
+    }
+    if (end != kTextEnd && start > end) {
+        err = "text window starts after its end";
+        return CRDT_HIP_EINVAL;
+    }
+    return CRDT_HIP_OK;
+}
+
+int text_check_window(uint64_t start, uint64_t end, uint64_t total, bool inside, const TextInfo& w,
+                      const uint8_t* out, size_t cap, size_t* out_len, TextInfo* info, std::string& err) {
+    if (start > total || end > total) {
+        err = "text window beyond the version";
+        return CRDT_HIP_ERANGE;
+    }
+    if (inside) {
+        err = "text window boundary inside a codepoint";
+        return CRDT_HIP_EINVAL;
+    }
+    if (w.n_bytes >= (1ull << 32)) {
+        err = "a text window of 4 GiB or more";
+        return CRDT_HIP_ERANGE;
+    }
+    *out_len = (size_t)w.n_bytes;
+    if (info) *info = w;
+    if (w.n_bytes && (!out || cap < w.n_bytes)) {
+        err = "buffer too small";
+        return CRDT_HIP_ESPACE;
+    }
+    return CRDT_HIP_OK;
+}
+
+int OpLog::text_at(const LogMark* m, uint64_t start, uint64_t end, uint32_t flags, uint8_t* out,
+                   size_t cap, size_t* out_len, TextInfo* info, std::string& err) const {
+    if (m && (size() < m->n || m->deleted.size() != m->n)) {
+        err = "the log holds fewer items than the mark";
+        return CRDT_HIP_EINVAL;
+    }
+    int rc = text_check(start, end, flags, out_len, err);
+    if (rc) return rc;
+    const bool bytes = (flags & kTextBytes) != 0;
+    std::vector<uint32_t> order;
+    err = document_order(order);
+    if (!err.empty()) return CRDT_HIP_EBADLOG;
+    auto selected = [&](uint32_t id) {
+        return m ? id <= m->n && !m->deleted[id - 1] : !deleted[id - 1];
+    };
+    // one walk: the totals, and each boundary where the unit's running count meets it (a gap
+    // between two selected items, the start or the end of the version)
+    TextInfo w{};
+    uint64_t c = 0, b = 0, end_c = 0, end_b = 0;
+    bool got_start = false, got_end = false;
+    auto gap = [&]() {
+        const uint64_t p = bytes ? b : c;
+        if (!got_start && p == start) {
+            got_start = true;
+            w.start = c;
+            w.start_bytes = b;
+        }
+        if (!got_end && p == end) {
+            got_end = true;
+            end_c = c;
+            end_b = b;
+        }
+    };
+    for (uint32_t id : order) {
+        if (!selected(id)) continue;
+        gap();
+        ++c;
+        b += utf8_len_cp(cp[id - 1]);
+    }
+    if (end == kTextEnd) end = bytes ? b : c;
+    gap();
+    w.len = c;
+    w.len_bytes = b;
+    w.n = end_c - w.start;
+    w.n_bytes = end_b - w.start_bytes;
+    rc = text_check_window(start, end, bytes ? b : c, !got_start || !got_end, w, out, cap, out_len,
+                           info, err);
+    if (rc || w.n_bytes == 0) return rc;
+    uint64_t k = 0;  // selected items so far
+    uint8_t* o = out;
+    for (uint32_t id : order) {
+        if (!selected(id)) continue;
+        if (k >= w.start + w.n) break;
+        if (k++ < w.start) continue;
+        o += utf8_put(cp[id - 1], reinterpret_cast<char*>(o));
+    }
+    return CRDT_HIP_OK;
+}
+
 // ---- anchors -----------------------------------------------------------------------------------
 int anchor_check_at(const uint64_t* pos, const uint8_t* bias, size_t n, uint64_t visible,
                     std::string& err) {

@@ -133,6 +133,23 @@ struct EditPlanBytes {
 int edit_plan_bytes(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
                     uint64_t visible_bytes, uint64_t items, EditPlanBytes& plan, std::string& err);
 
+// Text windows (crdt_hip.h, "text windows"; the device twin is text.hip).  Layout of
+// crdt_hip_text_info.
+constexpr uint64_t kTextEnd = ~0ull;
+constexpr uint32_t kTextBytes = 1;
+struct TextInfo {
+    uint64_t len, len_bytes, start, start_bytes, n, n_bytes;
+};
+// The checks of a text_at call that need no document, shared by the host and the device path, in
+// their order: flags other than 0 or kTextBytes, out_len null, start > end (EINVAL).
+int text_check(uint64_t start, uint64_t end, uint32_t flags, const size_t* out_len, std::string& err);
+// And those that need the version's lengths and the boundaries, in their order: start or end
+// beyond `total` (the version's length in the unit asked; ERANGE), a byte boundary inside a
+// codepoint (EINVAL), a window of 4 GiB or more (ERANGE), then ESPACE with *out_len and *info set.
+// On success *out_len and *info are set too.  end: already resolved (kTextEnd -> total).
+int text_check_window(uint64_t start, uint64_t end, uint64_t total, bool inside, const TextInfo& w,
+                      const uint8_t* out, size_t cap, size_t* out_len, TextInfo* info, std::string& err);
+
 // Anchors (crdt_hip.h, "anchors"; the device twin is anchor.hip): a place in the text named by the
 // identity of the item next to it.  Layouts of crdt_hip_anchor and crdt_hip_anchor_pos.
 constexpr uint64_t kAnchorEdge = ~0ull;
@@ -261,6 +278,14 @@ public:
     // one patch deletes 4 GiB or more.
     int patches_since_bytes(const LogMark& m, std::vector<PatchRec>& out, std::vector<uint8_t>& ins,
                             std::string& err) const;
+    // A window of a version's text (crdt_hip.h, "text windows"): the version now (m null) or at a
+    // mark, [start, end) in codepoints or, with kTextBytes, in UTF-8 bytes (kTextEnd: the version's
+    // end).  The definition the device path (text.hip) is held to: the order comes from
+    // document_order per call, O(items); the positional index is neither read nor touched.  The
+    // checks run in the order crdt_hip.h states, from "fewer items than the mark" on; on any error
+    // but ESPACE out, *out_len and *info are untouched.  out_len may be null only to be refused.
+    int text_at(const LogMark* m, uint64_t start, uint64_t end, uint32_t flags, uint8_t* out,
+                size_t cap, size_t* out_len, TextInfo* info, std::string& err) const;
     // Local edits as a set of positional patches in the patches_since convention (crdt_hip.h,
     // "local edits"): validated up front (edit_plan, then the lamport bound and the positional
     // index), and a rejected call changes nothing; then remove + insert per patch, in order, which

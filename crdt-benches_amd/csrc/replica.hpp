@@ -315,6 +315,23 @@ int replica_spans(Engine& E, Replica& r, const FormatRec* f, size_t n, SpanRec* 
                   size_t* out_n, SpanAttrRec* attrs, size_t attr_cap, size_t* out_attrs,
                   size_t* pending, FormatStats* stats = nullptr);
 
+// Text windows (text.hip; semantics in crdt_hip.h, host twin OpLog::text_at).
+struct TextStats {  // what the last device text_at observed (crdt_hip_text_stats)
+    uint64_t ranks = 0;          // ranks of the document order streamed (the items held)
+    uint64_t tiles_written = 0;  // tiles the write pass launched a workgroup for
+    uint64_t bytes = 0;          // bytes returned
+    uint64_t device_ns = 0;      // summed device time of the call's kernels (HIP events)
+};
+struct TextInfo;
+// Settles a pending decode, runs the checks of crdt_hip.h in their order (m null: the version now),
+// brings r.inc up to date as replica_merge_inc does, counts and scans under the version's predicate,
+// waits once for the totals and the window, and writes only the tiles the window overlaps.
+// *out_len and *info are written by a call that succeeds and with ESPACE (before the write pass);
+// out only by a call that succeeds.
+int replica_text_at(Engine& E, Replica& r, const DeviceMark* m, uint64_t start, uint64_t end,
+                    uint32_t flags, uint8_t* out, size_t cap, size_t* out_len, TextInfo* info,
+                    TextStats* stats = nullptr);
+
 // Incremental merge (incr.hip): the merged text (may be null), its UTF-8 bytes and codepoints;
 // *path = 1 when only the items appended since the previous merge_inc were ranked, 0 for a
 // full merge (the first call, a concurrent update, more than kIncMax new items, Fugue).

@@ -384,6 +384,76 @@ int crdt_hip_oplog_patches_since(crdt_hip_oplog* log, const crdt_hip_mark* m, cr
                                  size_t cap, size_t* out_n, uint8_t* ins, size_t ins_cap,
                                  size_t* out_ins);
 
+/* ---- text windows: a range of the document, now or at a mark -----------------------------------
+ * An editor paints a viewport, not the document, and every system this project models itself on
+ * can read an old version (diamond-types' checkout(version), yrs' snapshots, automerge's
+ * text_at(heads)).  One read call takes a version (now, or a mark) and a window and returns that
+ * UTF-8 and nothing else, on the host (crdt_hip_oplog_text_at) and in HIP kernels on the device
+ * (crdt_hip_replica_text_at), with identical bytes and identical `info`.
+ *
+ * Everything is defined over the document order of all items held, tombstones included (RGA
+ * pre-order or Fugue in-order, as for patches_since and anchors).
+ *
+ * Versions.  m == NULL is the version now: item s is selected iff it is not tombstoned.  With a
+ * mark, s is selected iff s <= n_mark and it was not deleted at the mark.  The version's text is the
+ * UTF-8 of the selected items in document order.  Later items never reorder earlier ones, so
+ * text_at(mark) is byte for byte the text the owner had when the mark was taken, whatever updates,
+ * joins, deltas and local edits came since; and for every mark, applying patches_since(mark) to
+ * text_at(mark) gives the text now.
+ *
+ * Window.  [start, end) of that version, in codepoints, or in UTF-8 bytes with
+ * CRDT_HIP_TEXT_BYTES; end == CRDT_HIP_TEXT_END is the version's end.  `info` may be NULL; it
+ * reports the whole version and the window in both units, which is a position translation for
+ * free.  An empty window, an empty version and an empty log are all ok and give *out_len = 0 (and
+ * need no buffer: `out` may then be NULL).
+ *
+ * Checks, in this order.  On any error but ESPACE, `out`, *out_len and *info are untouched;
+ * nothing in the log or the replica ever changes.
+ *   1. CRDT_HIP_EINVAL  a mark of another owner (a clone is another owner); a host mark passed to
+ *                       the replica call or the reverse; a replica of another context; an owner
+ *                       with fewer items than the mark (the patches_since rules)
+ *   2. CRDT_HIP_EINVAL  flags other than 0 or CRDT_HIP_TEXT_BYTES; out_len == NULL
+ *   3. CRDT_HIP_EINVAL  start > end, when end is not CRDT_HIP_TEXT_END
+ *   4. CRDT_HIP_ERANGE  start, or an end that is not CRDT_HIP_TEXT_END, beyond the version's length
+ *                       in the unit asked
+ *   5. CRDT_HIP_EINVAL  (bytes) a start or end inside a codepoint of that version
+ *   6. CRDT_HIP_ERANGE  a window of 4 GiB or more
+ *   7. CRDT_HIP_ESPACE  a window of n_bytes > 0 with `out` NULL or cap < n_bytes: *out_len and
+ *                       *info are set and `out` is untouched
+ *
+ * The host call is the definition, not a product path: it takes the order from the log itself per
+ * call, O(items), and neither reads nor disturbs the resolver index; a malformed log is
+ * CRDT_HIP_EBADLOG.  The device call is the product.  It settles a pending decode and brings the
+ * kept document order up to date exactly as crdt_hip_replica_patches_since does (so a call leaves
+ * the replica as a merge_inc would), and makes no host copy of the replica's columns.  It counts the
+ * selected codepoints and bytes per tile of 4,096 ranks under the version's predicate (the mark's
+ * bit plane is never read for a slot above n_mark), scans the tile aggregates in one workgroup
+ * (64-bit prefixes), which also finds the tiles of `start` and `end` and walks each, a wave per
+ * boundary, to the boundary's codepoints and bytes; the host waits here once, runs checks 4 to 7
+ * (ESPACE comes before the write pass) and launches the write pass over the tiles the window
+ * overlaps only; the result is copied out in one transfer.  Known cost: a call streams every rank
+ * of the replica once, however small the window; after a join or a delta it first pays the full
+ * ORDER-mode rebuild. */
+#define CRDT_HIP_TEXT_END 0xFFFFFFFFFFFFFFFFull      /* `end`: the end of the version */
+enum { CRDT_HIP_TEXT_BYTES = 1 };                    /* flags: start/end count UTF-8 bytes */
+typedef struct {
+    uint64_t len, len_bytes;      /* the whole version: visible codepoints / UTF-8 bytes */
+    uint64_t start, start_bytes;  /* the window's start in both units */
+    uint64_t n, n_bytes;          /* the window's codepoints / bytes (n_bytes == *out_len) */
+} crdt_hip_text_info;
+int crdt_hip_oplog_text_at(crdt_hip_oplog* log, const crdt_hip_mark* m, uint64_t start, uint64_t end,
+                           uint32_t flags, uint8_t* out, size_t cap, size_t* out_len,
+                           crdt_hip_text_info* info);
+int crdt_hip_replica_text_at(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_mark* m,
+                             uint64_t start, uint64_t end, uint32_t flags, uint8_t* out, size_t cap,
+                             size_t* out_len, crdt_hip_text_info* info);
+/* What the context's last crdt_hip_replica_text_at observed (each may be NULL): ranks of the
+ * document order streamed (the items held), tiles the write pass launched a workgroup for, bytes
+ * returned, and the summed device time of the call's own kernels in ns (HIP events; the order
+ * update is not included). */
+int crdt_hip_text_stats(const crdt_hip_ctx* ctx, uint64_t* ranks, uint64_t* tiles_written,
+                        uint64_t* bytes, uint64_t* device_ns);
+
 /* ---- local edits: positional patches into a log or a replica ----------------------------------
  * The inverse of patches_since: a set of positional patches applied as local edits, on the host
  * (crdt_hip_oplog_apply_patches) or, in HIP kernels, to a replica where it lies
