@@ -24,8 +24,9 @@
 //   k_anchor_create   a wave per position: a binary search of the scanned prefixes for the tile that
 //                     holds the first visible item whose inclusive prefix reaches the position (AFTER)
 //                     or passes it (BEFORE), then a walk of that tile 64 ranks a step with a wave
-//                     scan; the item's lane writes jident(key[slot]).  In bytes an item whose prefix
-//                     steps over the position without meeting it raises EA_INSIDE (EINVAL)
+//                     scan (seek_tile and seek_step, view.hpp); the item's lane writes
+//                     jident(key[slot]).  In bytes an item whose prefix steps over the position
+//                     without meeting it raises EA_INSIDE (EINVAL)
 //
 // Per position a search, not every visible item searching a sorted position table as
 // k_edit_resolve does: positions come unsorted and repeated, a cursor batch is small, and a walk
@@ -58,7 +59,7 @@ namespace {
 
 // device counters (u64), after the B_N of the count
 enum ACtl { A_ERR = 0, A_UNKNOWN, A_N };
-// A_ERR bits, after EL_SLOT, EL_RANK and EL_TABLE (locate.hpp)
+// A_ERR bits, after E_ORD_SLOT (order.hpp), EL_RANK and EL_TABLE (locate.hpp)
 constexpr uint64_t EA_INSIDE = 8;  // a byte position inside a codepoint
 constexpr uint64_t EA_WALK = 16;   // a position's item is not in the tile the prefixes name
 
@@ -146,39 +147,28 @@ __global__ __launch_bounds__(kJB) void k_anchor_create(AnchorArgs a) {
         if (lane == 0) a.aout[i] = o;
         return;
     }
-    // the item: the first visible one whose inclusive prefix is at least thr; its tile: the last
-    // whose exclusive prefix is below thr (thr >= 1, and tile 0's is 0)
+    // the item: the first visible one whose inclusive prefix is at least thr (thr >= 1)
+    // (seek_tile and seek_step of view.hpp, a step's loads as the walk goes: view_seek's chunks of
+    // 16 steps take 69 / 72 VGPRs and 104 SGPRs here and the kernel to 7 waves a SIMD)
     const uint64_t thr = b == kAnchorAfter ? p : p + 1;
-    auto pre = [&](uint32_t t) { return BYTES ? a.v.tbpre[t] : (uint64_t)a.v.tcount[t]; };
-    uint32_t lo = 0, hi = a.v.ntiles;  // (not last_at_most: a strict <, and tile 0 always qualifies)
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (pre(mid) < thr) lo = mid;
-        else hi = mid;
-    }
-    uint64_t run = pre(lo);
-    bool found = false;
-    for (uint32_t st = 0; st < kOrderTile / 64u && !found; ++st) {
+    Seek f = seek_tile(a.v, BYTES, thr);
+    for (uint32_t st = 0; st < kOrderTile / 64u && !f.found; ++st) {
         uint32_t sl;
-        const uint32_t len = view_len(a.v, (uint64_t)lo * kOrderTile + st * 64u + lane, sl, err);
-        const uint32_t wt = BYTES ? len : (len ? 1u : 0u);
-        const uint32_t inw = wave_incl_scan(wt);
-        const uint64_t inc = run + inw;
-        const bool hit = wt != 0 && inc >= thr && inc - wt < thr;
-        found = __ballot(hit) != 0;  // (at most one lane: the prefixes ascend strictly over items)
-        if (hit) {
+        const uint32_t len = order_len_at(a.v.seq, a.v.cp, a.v.n, SelNow{},
+                                          (uint64_t)f.tile * kOrderTile + st * 64u + lane, sl, err);
+        seek_step(f, BYTES, thr, lane, len, sl, [&](uint64_t inc_c, uint64_t inc_b, uint32_t l, uint32_t s) {
             // AFTER: the item ends at p.  BEFORE: it starts at p.  (In codepoints always so.)
-            if (b == kAnchorAfter ? inc == p : inc - wt == p) {
-                const uint64_t k = a.v.key[sl];
+            const uint64_t inc = BYTES ? inc_b : inc_c;
+            if (b == kAnchorAfter ? inc == p : inc - (BYTES ? l : 1u) == p) {
+                const uint64_t k = a.v.key[s];
                 o.id = a.fugue ? jident<true>(k) : jident<false>(k);
                 a.aout[i] = o;
             } else {
                 err |= EA_INSIDE;
             }
-        }
-        run += (uint32_t)__builtin_amdgcn_readlane((int)inw, 63);
+        });
     }
-    if (!found) err |= EA_WALK;
+    if (!f.found) err |= EA_WALK;
     ctl_or(&a.ctl[A_ERR], err);
 }
 
@@ -226,7 +216,7 @@ int anchor_end(Engine& E, Replica& r, AnchorCall& c, const T* dev, std::vector<T
     // (a slot that is no item: the count met it before any walk here did, and its check says so)
     if (int rc = bytes_count_check(E, r, h, "anchors", "items")) return rc;
     if (e & ~EA_INSIDE) {
-        E.err = e & EL_SLOT    ? "anchors: the kept document order names a slot that is no item"
+        E.err = e & E_ORD_SLOT ? "anchors: the kept document order names a slot that is no item"
                 : e & EL_RANK  ? "anchors: the kept inverse order disagrees with the order"
                 : e & EL_TABLE ? "anchors: the identity table did not take every anchor"
                                : "anchors: a position's item is not where the tile prefixes say";

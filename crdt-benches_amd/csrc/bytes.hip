@@ -12,9 +12,9 @@
 //
 //   k_bytes_init       counters, and the boundaries of every patch set to "not found"
 //   k_bytes_count      a workgroup per tile of kOrderTile = 4,096 consecutive ranks, four ranks per
-//                      thread (order.hpp): the tile's visible items and their UTF-8 bytes
-//   k_bytes_top        one workgroup scans both; the byte prefixes are 64-bit (a tile holds at most
-//                      16 KiB, a replica may hold more than 2^32 bytes)
+//                      thread: the tile's visible items and their UTF-8 bytes (order_tile_count)
+//   k_bytes_top        one workgroup scans both (order_tile_scan); the byte prefixes are 64-bit (a
+//                      tile holds at most 16 KiB, a replica may hold more than 2^32 bytes)
 //   k_bytes_translate  each tile recomputes, per visible item, its visible rank v and the byte end
 //                      b of the document up to and including it (rank 0, the document start:
 //                      (0, 0)), binary-searches the byte table for the last patch with
@@ -46,53 +46,18 @@ __global__ __launch_bounds__(kJB) void k_bytes_init(BytesArgs a) {
     }
 }
 
-// The UTF-8 lengths of the thread's four ranks k0..k0 + 3 (0: no visible item there).
-__device__ __forceinline__ void bytes_load(const BytesArgs& a, uint64_t k0, uint32_t w[kOrdPer],
-                                           uint64_t& err) {
-#pragma unroll
-    for (uint32_t j = 0; j < kOrdPer; ++j) w[j] = 0;
-    order_load4(a.seq, a.cp, a.n, k0, err, EB_SLOT, [&](uint32_t j, uint32_t, uint32_t c) {
-        if (!(c & kDelBit)) w[j] = utf8_len(c & 0x001FFFFFu);
-    });
-}
-
 __global__ __launch_bounds__(kOrdT) void k_bytes_count(BytesArgs a) {
     __shared__ uint32_t red[kOrdW];
-    const uint64_t k0 = (uint64_t)blockIdx.x * kOrderTile + (uint64_t)threadIdx.x * kOrdPer;
-    uint32_t w[kOrdPer];
-    uint64_t err = 0;
-    bytes_load(a, k0, w, err);
-    ctl_or(&a.ctl[B_ERR], err);
-    uint32_t c = 0, b = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kOrdPer; ++j) {
-        c += w[j] ? 1u : 0u;
-        b += w[j];
-    }
-    const uint32_t tc = block_sum_t0<kOrdW>(c, red), tb = block_sum_t0<kOrdW>(b, red);
-    if (threadIdx.x == 0 && blockIdx.x < a.ntiles) {
-        a.tcount[blockIdx.x] = tc;
-        a.tbytes[blockIdx.x] = tb;
-    }
+    order_tile_count(a.seq, a.cp, a.n, SelNow{}, a.ntiles, a.tcount, a.tbytes, &a.ctl[B_ERR], red);
 }
 
 __global__ __launch_bounds__(kOrdTop) void k_bytes_top(BytesArgs a) {
     __shared__ uint32_t lds[kOrdTop / 64];
-    uint64_t c_vis = 0, c_b = 0;
-    for (uint32_t base = 0; base < a.ntiles; base += kOrdTop) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t c = i < a.ntiles ? a.tcount[i] : 0u, b = i < a.ntiles ? a.tbytes[i] : 0u;
-        uint32_t tot;
-        const uint32_t ec = block_excl_scan<kOrdTop / 64>(c, lds, tot);
-        if (i < a.ntiles) a.tcount[i] = (uint32_t)c_vis + ec;  // (at most n < 2^31)
-        c_vis += tot;
-        const uint32_t eb = block_excl_scan<kOrdTop / 64>(b, lds, tot);  // (a round: at most 4 MiB)
-        if (i < a.ntiles) a.tbpre[i] = c_b + eb;
-        c_b += tot;
-    }
+    uint64_t vis, visb;
+    order_tile_scan(a.ntiles, a.tcount, a.tbytes, a.tbpre, lds, vis, visb);
     if (threadIdx.x == 0) {
-        a.ctl[B_VIS] = c_vis;
-        a.ctl[B_VISB] = c_b;
+        a.ctl[B_VIS] = vis;
+        a.ctl[B_VISB] = visb;
     }
 }
 
@@ -100,9 +65,9 @@ __global__ __launch_bounds__(kOrdT) void k_bytes_translate(BytesArgs a) {
     __shared__ uint32_t lds[kOrdW];
     if (blockIdx.x >= a.ntiles) return;
     const uint64_t k0 = (uint64_t)blockIdx.x * kOrderTile + (uint64_t)threadIdx.x * kOrdPer;
-    uint32_t w[kOrdPer];
+    uint32_t w[kOrdPer], cpw[kOrdPer];
     uint64_t err = 0;
-    bytes_load(a, k0, w, err);  // (k_bytes_count reported any bad slot)
+    order_lens4(a.seq, a.cp, a.n, SelNow{}, k0, w, cpw, err);  // (k_bytes_count reported any bad slot)
     uint32_t c = 0, bs = 0;
 #pragma unroll
     for (uint32_t j = 0; j < kOrdPer; ++j) {
@@ -170,7 +135,7 @@ void bytes_count_enqueue(const BytesArgs& a, hipStream_t s) {
 }
 
 int bytes_count_check(Engine& E, const Replica& r, const uint64_t* c, const char* who, const char* what) {
-    if (c[B_ERR] & EB_SLOT) {
+    if (c[B_ERR] & E_ORD_SLOT) {
         E.err = std::string(who) + ": the kept document order names a slot that is no item";
         return CRDT_HIP_EBADLOG;
     }

@@ -15,8 +15,7 @@ namespace crdt {
 
 // device counters (u64) of a translation
 enum BCtl { B_ERR = 0, B_VIS, B_VISB, B_STARTS, B_ENDS, B_NDEL, B_N };
-// B_ERR bits
-constexpr uint64_t EB_SLOT = 1;   // the order names a slot that is no item of the replica
+// B_ERR bits, after E_ORD_SLOT (order.hpp)
 constexpr uint64_t EB_TABLE = 2;  // a patch whose end was found before its start
 
 // Device pointers only; the caller owns every array.

@@ -481,7 +481,7 @@ int replica_apply_patches_bytes(Engine& E, Replica& r, const PatchRec* p, size_t
     HIPTRY(E, hipStreamSynchronize(s), "byte translation sync");  // the wait the byte form adds
     sc.time_add();
     const uint64_t* c = sc.hctl + E_N;
-    if (c[B_ERR] == EB_TABLE) {  // (with EB_SLOT too, the check below names the slot first)
+    if (c[B_ERR] == EB_TABLE) {  // (with E_ORD_SLOT too, the check below names the slot first)
         E.err = "edit: a patch ends before it starts";
         return CRDT_HIP_EBADLOG;
     }

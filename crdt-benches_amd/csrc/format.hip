@@ -66,7 +66,7 @@ namespace {
 
 // device counters (u64), after the B_N of the count
 enum FCtl { F_ERR = 0, F_PENDING, F_BOUNDS, F_SEGS, F_LIVE, F_SPANS, F_ATTRS, F_N };
-// F_ERR bits, after EL_SLOT, EL_RANK and EL_TABLE (locate.hpp)
+// F_ERR bits, after E_ORD_SLOT (order.hpp), EL_RANK and EL_TABLE (locate.hpp)
 constexpr uint64_t EF_BOUND = 8;  // a boundary, segment, span or attr index outside its array
 constexpr uint64_t EF_RANGE = 16;  // 2^32 or more attributes
 
@@ -387,7 +387,7 @@ int fmt_fail(Engine& E, uint64_t e) {
         E.err = "spans: 2^32 or more span attributes";
         return CRDT_HIP_ERANGE;
     }
-    E.err = e & EL_SLOT    ? "spans: the kept document order names a slot that is no item"
+    E.err = e & E_ORD_SLOT ? "spans: the kept document order names a slot that is no item"
             : e & EL_RANK  ? "spans: the kept inverse order disagrees with the order"
             : e & EL_TABLE ? "spans: the identity table did not take every anchor"
                            : "spans: a boundary or a segment lies outside the call's arrays";

@@ -1,7 +1,7 @@
 // locate.hpp — what the kernels that turn the identities of a batch (anchors, format ends) into
-// positions share (anchor.hip, format.hip): a read-only view of the document order a replica keeps
-// after a merge_inc with the tile prefixes of bytes.hip's count, the walk of one tile of it, and the
-// identity lookup of a batch: the init part, the insert and probe kernels, and "anchor -> rank".
+// positions share (anchor.hip, format.hip): the view of the kept document order with its walk and
+// seek (view.hpp, which text.hip takes alone) and the identity lookup of a batch: the init part, the
+// insert and probe kernels, and "anchor -> rank".
 // Header-only, internal linkage (the library has no relocatable device code).
 //
 // No atomic here decides an order.  k_locate_insert claims a table entry with a CAS: which of the
@@ -14,60 +14,15 @@
 #include "idtab.hpp"
 #include "oplog.hpp"
 #include "order.hpp"
+#include "view.hpp"
 #include "wave.hpp"
 
 namespace crdt {
 namespace {
 
-// error bits, the same in A_ERR (anchor.hip) and F_ERR (format.hip)
-constexpr uint64_t EL_SLOT = 1;   // the order names a slot that is no item of the replica
+// error bits, the same in A_ERR (anchor.hip) and F_ERR (format.hip), after E_ORD_SLOT (order.hpp)
 constexpr uint64_t EL_RANK = 2;   // the inverse order names no rank, or not the slot's
 constexpr uint64_t EL_TABLE = 4;  // the identity table did not take an anchor
-
-struct OrderView {
-    const uint32_t* seq;     // rank -> slot, ranks 0..n
-    const uint32_t* rank;    // slot -> rank, slots 0..n
-    const uint8_t* cp;       // 3-byte codepoint words of slots 0..n
-    const uint64_t* key;
-    uint32_t n;              // items held
-    uint32_t ntiles;         // tiles of kOrderTile ranks (and gaps)
-    const uint32_t* tcount;  // per tile: visible items before it
-    const uint64_t* tbpre;   //   and their UTF-8 bytes
-    const uint64_t* vis;     // the visible items and bytes of the whole order (B_VIS, B_VISB)
-};
-
-// The UTF-8 length of the visible item at rank k (0: rank 0, a rank past n, a tombstone, or a slot
-// that is no item, which also raises EL_SLOT); sl: its slot.
-__device__ __forceinline__ uint32_t view_len(const OrderView& v, uint64_t k, uint32_t& sl, uint64_t& err) {
-    sl = 0;
-    if (k == 0 || k > v.n) return 0;
-    sl = v.seq[k];
-    if (sl == 0 || sl > v.n) {
-        err |= EL_SLOT;
-        sl = 0;
-        return 0;
-    }
-    const uint32_t c = cp3_get(v.cp, sl);
-    return c & kDelBit ? 0u : utf8_len(c & kDeltaCpMask);
-}
-
-// The visible codepoints and UTF-8 bytes at the ranks below `end`: the prefixes of `tile` (below
-// ntiles, and end at most its last rank + 1: the caller's) and a walk of the tile's ranks before
-// `end`, 64 a step.  Called by a whole wave.
-__device__ __forceinline__ void view_walk(const OrderView& v, uint32_t tile, uint32_t end, uint32_t lane,
-                                          uint64_t& pos, uint64_t& posb, uint64_t& err) {
-    const uint64_t pre = v.tcount[tile], preb = v.tbpre[tile];  // (in flight during the walk)
-    uint32_t cnt = 0, by = 0;
-    for (uint32_t k0 = tile * kOrderTile; k0 < end; k0 += 64u) {
-        uint32_t sl;
-        const uint32_t wt = k0 + lane < end ? view_len(v, k0 + lane, sl, err) : 0u;
-        cnt += (uint32_t)__popcll(__ballot(wt != 0));
-        by += wt;
-    }
-    by = wave_sum(by);  // (a tile holds at most 16 KiB)
-    pos = pre + cnt;
-    posb = preb + by;
-}
 
 // The identities a batch of m anchors names, and where the replica holds them.
 struct IdLookup {

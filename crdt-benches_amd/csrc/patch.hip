@@ -66,7 +66,7 @@ constexpr uint32_t C_NONE = 0, C_K = 1, C_D = 2, C_I = 3;
 
 // device counters (u64)
 enum PCtl { P_ERR = 0, P_PATCHES, P_IBYTES, P_NOW, P_DEL, P_N };
-constexpr uint64_t EP_SLOT = 1;   // the order names a slot that is no item of the replica
+// P_ERR bits, after E_ORD_SLOT (order.hpp)
 constexpr uint64_t EP_RANGE = 2;  // (bytes) one patch deletes 4 GiB or more
 
 // BYTES: pos and del count UTF-8 bytes instead of items (crdt_hip.h, "byte offsets").  A compile-
@@ -98,9 +98,8 @@ template <bool BYTES>
 struct PatchArgs {
     const uint32_t* seq;   // rank -> slot, ranks 0..n (rank 0 = slot 0, the document start)
     const uint8_t* cp;     // 3-byte codepoint words of slots 0..n
-    const uint64_t* mark;  // bit s: slot s was tombstoned at the mark, or is not an item
-    uint32_t n, n_mark;
-    uint64_t mark_words;
+    SelMark was;           // alive at the mark
+    uint32_t n;
     uint32_t ntiles;
     TileAgg* agg;
     TilePre<BYTES>* pre;
@@ -141,12 +140,10 @@ __device__ __forceinline__ void patch_load(const PatchArgs<BYTES>& a, uint64_t k
         cls[j] = C_NONE;
         cpw[j] = 0;
     }
-    order_load4(a.seq, a.cp, a.n, k0, err, EP_SLOT, [&](uint32_t j, uint32_t s, uint32_t c) {
-        const bool now = !(c & kDelBit);
-        const bool was = s <= a.n_mark && (uint64_t)(s >> 6) < a.mark_words &&
-                         !((a.mark[s >> 6] >> (s & 63u)) & 1ull);
+    order_load4(a.seq, a.cp, a.n, k0, err, E_ORD_SLOT, [&](uint32_t j, uint32_t s, uint32_t c) {
+        const bool now = SelNow{}(s, c), was = a.was(s, c);
         cls[j] = was ? (now ? C_K : C_D) : (now ? C_I : C_NONE);
-        cpw[j] = c & 0x001FFFFFu;
+        cpw[j] = c & kDeltaCpMask;
     });
 }
 
@@ -335,24 +332,7 @@ __global__ __launch_bounds__(kOrdT) void k_patch_write(PatchArgs<BYTES> a) {
         }
         if (c == C_I) {
             const uint32_t v = cpw[j], len = utf8_len(v);
-            if (ib + len <= a.nibytes) {
-                uint8_t* o = a.ins + ib;
-                if (len == 1) {
-                    o[0] = (uint8_t)v;
-                } else if (len == 2) {
-                    o[0] = (uint8_t)(0xC0u | (v >> 6));
-                    o[1] = (uint8_t)(0x80u | (v & 63u));
-                } else if (len == 3) {
-                    o[0] = (uint8_t)(0xE0u | (v >> 12));
-                    o[1] = (uint8_t)(0x80u | ((v >> 6) & 63u));
-                    o[2] = (uint8_t)(0x80u | (v & 63u));
-                } else {
-                    o[0] = (uint8_t)(0xF0u | (v >> 18));
-                    o[1] = (uint8_t)(0x80u | ((v >> 12) & 63u));
-                    o[2] = (uint8_t)(0x80u | ((v >> 6) & 63u));
-                    o[3] = (uint8_t)(0x80u | (v & 63u));
-                }
-            }
+            if (ib + len <= a.nibytes) utf8_store(a.ins + ib, v, len);
             ib += len;
         }
         if (c == C_D) del += item_w<BYTES>(cpw[j]);
@@ -428,10 +408,7 @@ int patches_since_impl(Engine& E, Replica& r, const DeviceMark& m, PatchRec* out
     HIPTRY(E, hipSetDevice(E.device), "hipSetDevice");
     int rc = replica_settle(E, r);
     if (rc) return rc;
-    if (r.n < m.n || !m.bits || m.words != ((uint64_t)m.n + 1 + 63) / 64) {
-        E.err = "the replica holds fewer items than the mark";
-        return CRDT_HIP_EINVAL;
-    }
+    if ((rc = mark_fits(E, r, m))) return rc;
     if (r.n == 0) return CRDT_HIP_OK;  // nothing held: nothing changed
     PatchArgs<BYTES> a{};
     rc = replica_kept_order(E, r, "patches", &a.seq, &a.ntiles);
@@ -439,10 +416,8 @@ int patches_since_impl(Engine& E, Replica& r, const DeviceMark& m, PatchRec* out
     hipStream_t s = E.stream;
     CallScratch sc(s);
     a.cp = r.logs.cp;
-    a.mark = m.bits;
+    a.was = SelMark{{m.bits, m.n, m.words}};
     a.n = r.n;
-    a.n_mark = m.n;
-    a.mark_words = m.words;
     HIPTRY(E, sc.counters(P_N), "hipMalloc patch counters");
     HIPTRY(E, sc.alloc(&a.agg, (uint64_t)a.ntiles), "hipMalloc patch tiles");
     HIPTRY(E, sc.alloc(&a.pre, (uint64_t)a.ntiles), "hipMalloc patch tiles");

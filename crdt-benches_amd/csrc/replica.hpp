@@ -214,6 +214,15 @@ struct DeviceMark {
     DeviceMark& operator=(const DeviceMark&) = delete;
     ~DeviceMark();
 };
+// What every call that reads a mark asks of it first (r settled): a mark of this replica's past, with
+// the plane its item count needs.  EINVAL otherwise.
+inline int mark_fits(Engine& E, const Replica& r, const DeviceMark& m) {
+    if (r.n < m.n || !m.bits || m.words != ((uint64_t)m.n + 1 + 63) / 64) {
+        E.err = "the replica holds fewer items than the mark";
+        return CRDT_HIP_EINVAL;
+    }
+    return CRDT_HIP_OK;
+}
 struct PatchStats {  // what the last device patches_since observed (crdt_hip_patch_stats)
     uint64_t patches = 0;    // patches found
     uint64_t ins_bytes = 0;  // their inserted UTF-8 bytes

@@ -91,10 +91,11 @@ def test_empty_and_one_item(pair, ctx, kind):
     assert t.resolve(ref, a)["state"].tolist() == [LIVE, DEAD, DEAD, LIVE]
 
 
-def chain_log(fugue: bool, n: int, dead_ranges, seed: int, width4_at=()) -> crdt_hip.OpLog:
+def chain_log(fugue: bool, n: int, dead_ranges, seed: int, width4_at=(), alive_at=()) -> crdt_hip.OpLog:
     """A log of n items typed in one piece (rank k = item k), cut to n through LogArrays, with
     about 20 % of its items tombstoned at random and every rank of `dead_ranges` (first, last)
-    tombstoned; the ranks of `width4_at` hold a visible 4-byte codepoint."""
+    tombstoned; the ranks of `width4_at` hold a visible 4-byte codepoint, those of `alive_at` a
+    visible item."""
     rng = random.Random(seed)
     text = list(text_of(rng, n + 50))
     for k in width4_at:
@@ -105,7 +106,7 @@ def chain_log(fugue: bool, n: int, dead_ranges, seed: int, width4_at=()) -> crdt
     deleted = np.array([1 if rng.random() < 0.2 else 0 for _ in range(n)], np.uint8)
     for first, last in dead_ranges:
         deleted[first - 1: last] = 1
-    for k in width4_at:
+    for k in (*width4_at, *alive_at):
         deleted[k - 1] = 0
     cut = crdt_hip.LogArrays(A.parent[:n], A.lamport[:n], A.agent[:n], deleted, A.cp[:n],
                              side=A.side[:n] if fugue else None)
@@ -152,6 +153,48 @@ def test_tile_edges(pair, ctx, kind, ranks):
         assert arrs.deleted[4094] and arrs.deleted[4095]
     got = t.resolve(ref, [(ident_of(arrs, s), b) for s in near for b in (AFTER, BEFORE)])
     assert {LIVE, DEAD} <= set(got["state"].tolist())
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("ranks", [4097, 8193])
+def test_chunk_edges(pair, kind, ranks):
+    """A walk that loads a tile in chunks of 16 steps has an edge every 1,024 ranks inside a tile.
+    k_anchor_create walks step by step today (the chunked view_seek is what text windows use): this
+    guards its switch to view_seek.  Positions whose item lies one rank below, at and one rank above each such edge of tiles 0 and 1,
+    under both biases, in codepoints and in bytes, round-tripped through resolve; ranks 1,024 and
+    1,025 hold visible 4-byte codepoints, so the offsets one to three bytes inside them are EINVAL.
+    A second replica has ranks 1,020..1,030 of each tile dead: the item a position there names is
+    the first one past the edge."""
+    fugue = kind == "fugue"
+    n = ranks - 1
+    named = [k for t in (0, 1) for c in (1024, 2048, 3072) for d in (-1, 0, 1)
+             for k in [t * TILE + c + d] if k <= n]
+    wide = [k for k in (1024, 1025, TILE + 1024, TILE + 1025) if k <= n]
+    stretch = [(t * TILE + 1020, t * TILE + 1030) for t in (0, 1) if t * TILE + 1030 <= n]
+    out = au.raw_anchors([(3, 1)])
+    for dead, width4, alive in (([], wide, named), (stretch, (), ())):
+        t = pair(chain_log(fugue, n, dead, ranks + 1, width4_at=width4, alive_at=alive), fugue)
+        ref = t.ref()
+        assert ref.order == list(range(1, n + 1))
+        rank_vis = {s: v + 1 for v, s in enumerate(ref.vis)}   # (rank k = item k) -> visible rank
+        assert all(k in rank_vis for k in alive) and not any(
+            k in rank_vis for lo, hi in dead for k in range(lo, hi + 1))
+        # the named ranks, or with a dead stretch over them the nearest visible item on either side
+        items = {k for k in named if k in rank_vis}
+        for lo, hi in dead:
+            items |= {max(k for k in rank_vis if k < lo), min(k for k in rank_vis if k > hi)}
+        gaps = sorted({g for k in items for g in (rank_vis[k] - 1, rank_vis[k])})
+        for in_bytes in (False, True):
+            pos = [ref.ends[p] for p in gaps] if in_bytes else gaps
+            pos, bias = pos + pos, [AFTER] * len(pos) + [BEFORE] * len(pos)
+            back = t.resolve(ref, t.at(ref, pos, bias, in_bytes))
+            assert back["pos_bytes" if in_bytes else "pos"].tolist() == pos
+        for k in width4:
+            for inside in (1, 2, 3):
+                p = ref.before[k][1] + inside
+                for b in (AFTER, BEFORE):
+                    for obj in (t.rep, t.host):
+                        au.fails(lambda o: obj.anchors_at_bytes_raw([p], b, out=o), EINVAL, out)
 
 
 @pytest.mark.parametrize("kind", KINDS)

@@ -141,6 +141,44 @@ def test_wide_codepoints_on_tile_edges(twin, kind):
 
 
 @pytest.mark.parametrize("kind", KINDS)
+def test_chunk_edges_of_a_boundary_walk(twin, kind):
+    """8,300 items typed in one run (rank r holds full[r - 1]).  A boundary's walk loads its tile in
+    chunks of 16 steps, an edge every 1,024 ranks inside a tile: windows that start and end with the
+    item one rank below, at and one rank above each such edge of tiles 0 and 1, at the mark (which
+    selects every rank) and now (ranks 501..510 and 1,020..1,030 of tile 1 dead, so every boundary
+    has moved and three of them fall together behind a dead stretch over an edge).  Ranks 1,024 and
+    1,025 hold 4-byte codepoints: a cut inside them is EINVAL."""
+    fugue = kind == "fugue"
+    cps = list(tu.mixed_text(8300, 17))
+    cps[1023] = cps[1024] = "😀"
+    full = "".join(cps)
+    t = twin(typed(fugue, full), fugue)
+    dm, hm, _ = t.mark()
+    dead = [(TILE + 1020, TILE + 1030), (501, 510)]             # ranks, the later stretch first
+    t.edit(lambda l: [l.remove(lo - 1, hi) for lo, hi in dead])
+    alive = [True] * (len(full) + 1)
+    for lo, hi in dead:
+        alive[lo:hi + 1] = [False] * (hi + 1 - lo)
+    now = "".join(full[k - 1] for k in range(1, len(full) + 1) if alive[k])
+    assert t.rep.text_at() == now.encode() and t.rep.text_at(dm) == full.encode()
+    named = [tile * TILE + c + d for tile in (0, 1) for c in (1024, 2048, 3072) for d in (-1, 0, 1)]
+    # the boundary behind the item of rank k: the selected items of ranks 1..k
+    for marks, text, ends in (((dm, hm), full, named),
+                              (None, now, sorted({sum(alive[1:k + 1]) for k in named}))):
+        bd = tu.boundaries(text)
+        cuts = [0] + ends + [len(text)]
+        for a, b in zip(cuts, cuts[1:]):
+            both(t, marks, text, a, b, bd)
+        both(t, marks, text, ends[0], ends[-1], bd)
+    bd = tu.boundaries(full)
+    for obj, mk in ((t.rep, dm), (t.host, hm)):
+        for i in (1023, 1024):
+            for k in (1, 2, 3):
+                tu.assert_refused(obj, mk, bd[i] + k, tu.END, tu.BYTES, tu.EINVAL)
+                tu.assert_refused(obj, mk, 0, bd[i] + k, tu.BYTES, tu.EINVAL)
+
+
+@pytest.mark.parametrize("kind", KINDS)
 def test_marks_far_below_the_replica(twin, kind):
     """Marks at 63, 64, 65 and 100 items, then 9,000 more items, some typed into the marked text:
     the replica holds slots far past each mark's bit plane.  Then everything the marks saw is
