@@ -37,9 +37,10 @@ def boundaries(text: str) -> list:
     return out
 
 
-def want_info(text: str, a: int, b: int) -> dict:
-    """crdt_hip_text_info of the codepoint window [a, b) of `text`."""
-    bd = boundaries(text)
+def want_info(text: str, a: int, b: int, bd=None) -> dict:
+    """crdt_hip_text_info of the codepoint window [a, b) of `text` (bd: its boundaries, if the
+    caller has them)."""
+    bd = bd or boundaries(text)
     return {"len": len(text), "len_bytes": bd[-1], "start": a, "start_bytes": bd[a], "n": b - a,
             "n_bytes": bd[b] - bd[a]}
 
@@ -81,7 +82,7 @@ def check_window(obj, mark, text: str, a: int, b: int, bd=None) -> None:
     slice and all six fields of the info, both ways, and text_info alone."""
     bd = bd or boundaries(text)
     want = text[a:b].encode("utf-8")
-    info = want_info(text, a, b)
+    info = want_info(text, a, b, bd)
     assert obj.text_at(mark, a, b) == want
     assert obj.text_info(mark, a, b) == info
     assert obj.text_at(mark, bd[a], bd[b], bytes=True) == want
