@@ -146,6 +146,46 @@ int replace_as_patch(crdt_hip_ctx* ctx, size_t start, size_t end, size_t nbytes,
     const crdt_hip_patch one{(uint64_t)start, 0, (uint32_t)del, (uint32_t)nbytes};
     return what(&one);
 }
+
+// The parameters of crdt_hip_set_param (all but "splitter_stride", which writes two knobs): the
+// ABI name, the knob (engine.hpp Tunables, where each is described), the accepted values and the
+// message for any other.  No message: a hook that takes any value, nonzero = on.
+using crdt::Tunables;
+template <uint64_t LO, uint64_t HI>
+bool within(uint64_t v) { return v >= LO && v <= HI; }
+bool runs_slots_ok(uint64_t v) { return v == 16 || v == 32 || v == 64; }
+bool digit_bits_ok(uint64_t v) { return v == 0 || v == 8 || v == 10; }
+struct Param {
+    const char* name;
+    uint64_t Tunables::*field;
+    bool (*ok)(uint64_t);
+    const char* msg;
+};
+const Param kParams[] = {
+    {"max_wave_slots", &Tunables::max_wave_slots, within<4096, 1ull << 31>, "max_wave_slots out of range"},
+    {"tail_wave_div", &Tunables::tail_wave_div, within<0, 64>, "tail_wave_div must be in [0, 64]"},
+    {"lanes", &Tunables::lanes, within<1, 8>, "lanes must be in [1, 8]"},
+    {"lane_gate", &Tunables::l0_gated, within<0, 1>, "lane_gate must be 0 or 1"},
+    {"l1_split", &Tunables::l1_split, within<0, 1>, "l1_split must be 0 or 1"},
+    {"plan_cache", &Tunables::plan_cache, within<0, 1>, "plan_cache must be 0 or 1"},
+    {"fuse_text", &Tunables::fuse_text, nullptr, nullptr},
+    {"doctree_lds_max", &Tunables::doctree_lds_max, nullptr, nullptr},
+    {"xcd_order", &Tunables::xcd_order, within<0, 1>, "xcd_order must be 0 or 1"},
+    {"group_docs", &Tunables::group_docs, within<0, 1>, "group_docs must be 0 or 1"},
+    {"runs_slots", &Tunables::runs_slots, runs_slots_ok, "runs_slots must be 16, 32 or 64"},
+    {"stile_text", &Tunables::stile_text, within<0, 2>, "stile_text must be 0, 1 or 2"},
+    {"text_scatter", &Tunables::text_scatter, within<0, 1>, "text_scatter must be 0 or 1"},
+    {"contraction", &Tunables::contraction, within<0, 2>, "contraction must be 0, 1 or 2"},
+    {"l1_group", &Tunables::l1_group, within<0, 2>, "l1_group must be 0, 1 or 2"},
+    {"rs_digit_bits", &Tunables::rs_digit_bits, digit_bits_ok, "rs_digit_bits must be 0, 8 or 10"},
+    {"nsq_list", &Tunables::nsq_list, within<0, 2>, "nsq_list must be 0, 1 or 2"},
+    {"static_jumps", &Tunables::static_jumps, within<0, 1>, "static_jumps must be 0 or 1"},
+    {"dead_skip", &Tunables::dead_skip, within<0, 1>, "dead_skip must be 0 or 1"},
+    {"doctree_k32", &Tunables::doctree_k32, within<0, 1>, "doctree_k32 must be 0 or 1"},
+    {"glds_late", &Tunables::glds_late, nullptr, nullptr},
+    {"plan_shrink", &Tunables::plan_shrink, nullptr, nullptr},
+    {"level1", &Tunables::level1_global, within<0, 1>, "level1 must be 0 (auto) or 1 (global)"},
+};
 }  // namespace
 
 extern "C" {
@@ -199,123 +239,14 @@ int crdt_hip_set_param(crdt_hip_ctx* ctx, const char* key, uint64_t value) {
         uint32_t l = 0;
         while ((1ull << l) < value) ++l;
         ctx->eng.log2m = l;
-        ctx->eng.log2m_set = true;
+        ctx->eng.log2m_set = 1;
         return 0;
     }
-    if (k == "max_wave_slots") {
-        if (value < 4096 || value > (1ull << 31))
-            return set_err(ctx, CRDT_HIP_EINVAL, "max_wave_slots out of range");
-        ctx->eng.max_wave_slots = value;
-        return 0;
-    }
-    if (k == "tail_wave_div") {
-        if (value > 64) return set_err(ctx, CRDT_HIP_EINVAL, "tail_wave_div must be in [0, 64]");
-        ctx->eng.tail_wave_div = (uint32_t)value;
-        return 0;
-    }
-    if (k == "lanes") {
-        if (value < 1 || value > 8) return set_err(ctx, CRDT_HIP_EINVAL, "lanes must be in [1, 8]");
-        ctx->eng.lanes = (uint32_t)value;
-        return 0;
-    }
-    if (k == "lane_gate") {
-        if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "lane_gate must be 0 or 1");
-        ctx->eng.l0_gated = value == 1;
-        return 0;
-    }
-    if (k == "l1_split") {
-        if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "l1_split must be 0 or 1");
-        ctx->eng.l1_split = value == 1;
-        return 0;
-    }
-    if (k == "plan_cache") {
-        if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "plan_cache must be 0 or 1");
-        ctx->eng.plan_cache = value == 1;
-        return 0;
-    }
-    if (k == "fuse_text") {  // 0: k_doctree leaves the text to k_expand (smaller LDS footprint)
-        ctx->eng.fuse_text = value != 0;
-        return 0;
-    }
-    if (k == "doctree_lds_max") {  // experiment hook (see Engine::doctree_lds_max)
-        ctx->eng.doctree_lds_max = value != 0;
-        return 0;
-    }
-    if (k == "xcd_order") {  // 1: XCD-aware tile order in level 0 (engine.hip xcd_block)
-        if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "xcd_order must be 0 or 1");
-        ctx->eng.xcd_order = value == 1;
-        return 0;
-    }
-    if (k == "group_docs") {  // replica batches: documents placed base by base (waves per base)
-        if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "group_docs must be 0 or 1");
-        ctx->eng.group_docs = value == 1;
+    for (const Param& p : kParams) {
+        if (k != p.name) continue;
+        if (p.msg && !p.ok(value)) return set_err(ctx, CRDT_HIP_EINVAL, p.msg);
+        ctx->eng.*p.field = p.msg ? value : (uint64_t)(value != 0);
         return CRDT_HIP_OK;
-    }
-    if (k == "runs_slots") {  // k_runs slots per thread: 16, 32 or 64
-        if (value != 16 && value != 32 && value != 64)
-            return set_err(ctx, CRDT_HIP_EINVAL, "runs_slots must be 16, 32 or 64");
-        ctx->eng.runs_slots = (uint32_t)value;
-        return CRDT_HIP_OK;
-    }
-    if (k == "stile_text") {  // fused plans stage text from the tile segments (L1Plan): 1 by
-                              // loads and shifts, 2 by LDS-DMA per tile
-        if (value > 2) return set_err(ctx, CRDT_HIP_EINVAL, "stile_text must be 0, 1 or 2");
-        ctx->eng.stile_text = (uint32_t)value;
-        return 0;
-    }
-    if (k == "text_scatter") {  // stile plans: 1 k_doctree + k_tscatter, 0 k_doctree phase C
-        if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "text_scatter must be 0 or 1");
-        ctx->eng.text_scatter = (uint32_t)value;
-        return CRDT_HIP_OK;
-    }
-    if (k == "contraction") {  // run contraction: 0 by the input, 1 always, 2 never (Wave::nocon)
-        if (value > 2) return set_err(ctx, CRDT_HIP_EINVAL, "contraction must be 0, 1 or 2");
-        ctx->eng.contraction = (uint32_t)value;
-        return CRDT_HIP_OK;
-    }
-    if (k == "l1_group") {  // global level-1 sibling grouping: 0 auto, 1 counting, 2 radix sorts
-        if (value > 2) return set_err(ctx, CRDT_HIP_EINVAL, "l1_group must be 0, 1 or 2");
-        ctx->eng.l1_group = (uint32_t)value;
-        return CRDT_HIP_OK;
-    }
-    if (k == "rs_digit_bits") {  // radix sort A's digit width: 0 auto, 8 or 10
-        if (value != 0 && value != 8 && value != 10)
-            return set_err(ctx, CRDT_HIP_EINVAL, "rs_digit_bits must be 0, 8 or 10");
-        ctx->eng.rs_digit_bits = (uint32_t)value;
-        return CRDT_HIP_OK;
-    }
-    if (k == "nsq_list") {  // the compact nsq parent list (Engine::build_nsq, nsq_launch)
-        if (value > 2) return set_err(ctx, CRDT_HIP_EINVAL, "nsq_list must be 0, 1 or 2");
-        ctx->eng.nsq_list = (uint32_t)value;
-        return 0;
-    }
-    if (k == "static_jumps") {  // resident jump bits, heads in k_classify (Engine::static_jumps)
-        if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "static_jumps must be 0 or 1");
-        ctx->eng.static_jumps = (uint32_t)value;
-        return CRDT_HIP_OK;
-    }
-    if (k == "dead_skip") {  // flag planes, codepoints of live groups only (Engine::dead_skip)
-        if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "dead_skip must be 0 or 1");
-        ctx->eng.dead_skip = (uint32_t)value;
-        return CRDT_HIP_OK;
-    }
-    if (k == "doctree_k32") {  // LDS level 1 with 32-bit sibling keys (Engine::doctree_k32)
-        if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "doctree_k32 must be 0 or 1");
-        ctx->eng.doctree_k32 = value == 1;
-        return CRDT_HIP_OK;
-    }
-    if (k == "glds_late") {  // test hook (see Engine::glds_late)
-        ctx->eng.glds_late = value != 0;
-        return 0;
-    }
-    if (k == "plan_shrink") {  // test hook (see Engine::plan_shrink)
-        ctx->eng.plan_shrink = value != 0;
-        return 0;
-    }
-    if (k == "level1") {
-        if (value > 1) return set_err(ctx, CRDT_HIP_EINVAL, "level1 must be 0 (auto) or 1 (global)");
-        ctx->eng.level1_global = value == 1;
-        return 0;
     }
     return set_err(ctx, CRDT_HIP_EINVAL, "unknown parameter " + k);
 }

@@ -4553,6 +4553,20 @@ int Engine::ensure_scratch(const Wave& w) {
     return CRDT_HIP_OK;
 }
 
+// Run heads and their text starts.  They are written before the run count is known: runs <= slots
+// (Fugue: rows <= 2 slots, a content and a tree row per head with left children).
+int Engine::ensure_heads(const DeviceLogs& L, const Wave& w) {
+    const uint64_t hrows = w.nslots * (L.fugue ? 2ull : 1ull);
+    if (hrows > cap_heads_) {
+        dfree(r_head_); dfree(r_pstart_);
+        HIPCHK(dalloc(&r_head_, hrows + 64ull), "hipMalloc r_head");
+        HIPCHK(dalloc(&r_pstart_, hrows + 64ull), "hipMalloc r_pstart");
+        cap_heads_ = hrows;
+        gen_++;
+    }
+    return CRDT_HIP_OK;
+}
+
 // Level-1 scratch, sized by the runs of the wave (known after level 0).
 int Engine::ensure_runs(uint64_t R, uint64_t S) {
     if (R > cap_runs_) {
@@ -4676,6 +4690,11 @@ L1Plan Engine::plan_level1(const Wave& w, uint32_t R, uint32_t rmax, bool ord,
                                         44ull * (w.max_doc_slots / kScanTile + 3u) + 15u) & ~15ull))
                          : dbytes;
     if (doctree_lds_max && p.lds1) p.dyn_bytes = kDocLds;  // experiment: one workgroup per CU
+    // splitter stride: longer sublists once the pointer jumping over the splitter lists
+    // dominates (measured on config 5: 182 M runs, stride 16 -> 64 took 72 -> 59 ms)
+    p.log2m = log2m_set ? (uint32_t)log2m : (R > (1u << 24) ? 6u : 4u);
+    p.Sreg = 2 * ((R + (1u << p.log2m) - 1) >> p.log2m);
+    p.S = p.Sreg + w.ndocs;
     return p;
 }
 
@@ -4695,78 +4714,84 @@ int Engine::clock_mark(StageClock& c, int stage) {
     } while (0)
 
 // Level-0 argument block of a wave (device pointers of L and of this engine's scratch).
-#define L0ARGS(a0)                                                  \
-    L0Args a0{};                                                    \
-    a0.nslots = w.nslots;                                           \
-    a0.log2m = L.log2m;                                             \
-    a0.ndocs = w.ndocs;                                             \
-    a0.mode = ord ? 1u : 0u;                                        \
-    a0.ntiles = (uint32_t)((w.nslots + kScanTile - 1) / kScanTile); \
-    a0.chunk_doc = L.chunk_doc + (w.slot0 >> L.log2m);              \
-    a0.docs = L.docs_rel + w.first_doc;                             \
-    a0.in_parent = L.parent + w.slot0;                              \
-    a0.in_key = L.key + w.slot0;                                    \
-    a0.in_cp = L.cp + 3ull * w.slot0;                               \
-    a0.sjump = static_wave(L, w) ? 1u : 0u;                         \
-    a0.jbits = a0.sjump ? L.jump + DeviceLogs::kJumpHead + (w.slot0 >> 5) : jbits_; \
-    a0.tomb = plane_wave(L, w, ord) ? reinterpret_cast<const uint16_t*>(L.tomb + (w.slot0 >> 6)) : nullptr; \
-    a0.nsqb = a0.tomb ? reinterpret_cast<uint16_t*>(L.nsq_mask + (w.slot0 >> 6)) : nsqb_; \
-    a0.wnib = wnib_;                                                \
-    a0.visb = visb_;                                                \
-    a0.escm = escm_;                                                \
-    a0.lbits = jbits_ + jbits_words(w.nslots);                      \
-    a0.fugue = L.fugue ? 1u : 0u;                                   \
-    a0.stile = stile_;                                              \
-    a0.plist = plist_;                                              \
-    a0.sbytes = sbytes_;                                            \
-    a0.sbytes_cap = cap_sbytes_ - 64;                               \
-    a0.tile_hw = tile_hw_;                                          \
-    a0.tile_sums = tile_sums_;                                      \
-    a0.hrec = hrec_;                                                \
-    a0.doc_root = doc_root_;                                        \
-    a0.doc_p0 = doc_p0_;                                            \
-    a0.ctl = ctl_;                                                  \
-    a0.r_head = r_head_;                                            \
-    a0.r_pstart = r_pstart_;                                        \
-    a0.r_parent = r_parent_;                                        \
-    a0.r_key = r_key_;                                              \
-    a0.cap_runs = 0xFFFFFFFFu;                                      \
-    a0.cap_rmax = 0xFFFFFFFFu;                                      \
-    a0.cap_rows = (uint32_t)std::min<uint64_t>(cap_runs_, 0xFFFFFFFFull);  \
-    a0.xcd = xcd_order ? 1u : 0u;                                  \
-    a0.nsq_par = L.nsq_ok ? L.nsq_par : nullptr;                    \
-    a0.nsq_key = L.nsq_ok ? L.nsq_key : nullptr;                    \
-    a0.nsq_pre = L.nsq_ok ? L.nsq_pre + (w.slot0 >> 6) : nullptr;   \
-    a0.nocon = w.nocon ? 1u : 0u;                                   \
-    a0.copy_text = 1u
+template <>
+L0Args Engine::wave_args<L0Args>(const DeviceLogs& L, const Wave& w, bool ord) const {
+    L0Args a0{};
+    a0.nslots = w.nslots;
+    a0.log2m = L.log2m;
+    a0.ndocs = w.ndocs;
+    a0.mode = ord ? 1u : 0u;
+    a0.ntiles = (uint32_t)((w.nslots + kScanTile - 1) / kScanTile);
+    a0.chunk_doc = L.chunk_doc + (w.slot0 >> L.log2m);
+    a0.docs = L.docs_rel + w.first_doc;
+    a0.in_parent = L.parent + w.slot0;
+    a0.in_key = L.key + w.slot0;
+    a0.in_cp = L.cp + 3ull * w.slot0;
+    a0.sjump = static_wave(L, w) ? 1u : 0u;
+    a0.jbits = a0.sjump ? L.jump + DeviceLogs::kJumpHead + (w.slot0 >> 5) : jbits_;
+    a0.tomb = plane_wave(L, w, ord) ? reinterpret_cast<const uint16_t*>(L.tomb + (w.slot0 >> 6)) : nullptr;
+    a0.nsqb = a0.tomb ? reinterpret_cast<uint16_t*>(L.nsq_mask + (w.slot0 >> 6)) : nsqb_;
+    a0.wnib = wnib_;
+    a0.visb = visb_;
+    a0.escm = escm_;
+    a0.lbits = jbits_ + jbits_words(w.nslots);
+    a0.fugue = L.fugue ? 1u : 0u;
+    a0.stile = stile_;
+    a0.plist = plist_;
+    a0.sbytes = sbytes_;
+    a0.sbytes_cap = text_room(cap_sbytes_);
+    a0.tile_hw = tile_hw_;
+    a0.tile_sums = tile_sums_;
+    a0.hrec = hrec_;
+    a0.doc_root = doc_root_;
+    a0.doc_p0 = doc_p0_;
+    a0.ctl = ctl_;
+    a0.r_head = r_head_;
+    a0.r_pstart = r_pstart_;
+    a0.r_parent = r_parent_;
+    a0.r_key = r_key_;
+    a0.cap_runs = 0xFFFFFFFFu;
+    a0.cap_rmax = 0xFFFFFFFFu;
+    a0.cap_rows = (uint32_t)std::min<uint64_t>(cap_runs_, 0xFFFFFFFFull);
+    a0.xcd = xcd_order ? 1u : 0u;
+    a0.nsq_par = L.nsq_ok ? L.nsq_par : nullptr;
+    a0.nsq_key = L.nsq_ok ? L.nsq_key : nullptr;
+    a0.nsq_pre = L.nsq_ok ? L.nsq_pre + (w.slot0 >> 6) : nullptr;
+    a0.nocon = w.nocon ? 1u : 0u;
+    a0.copy_text = 1u;
+    return a0;
+}
 
 // Tree / digest argument block (run counts come from ctl where the kernels need them).
-#define TREEARGS(a)                                                                   \
-    TreeArgs a{};                                                                     \
-    a.ndocs = w.ndocs;                                                                \
-    a.in_parent = r_parent_;                                                          \
-    a.key = r_key_;                                                                   \
-    a.pstart = r_pstart_;                                                             \
-    a.doc_root = doc_root_;                                                           \
-    a.doc_p0 = doc_p0_;                                                               \
-    a.rec = rec_; a.ctl = ctl_; a.swn = swn_;                                         \
-    a.roff = roff_;                                                                   \
-    a.rloc = rloc_;                                                                   \
-    a.tlen = tlen_; a.toff = toff_; a.loff = loff_; a.leafh = leafh_; a.ghash = ghash_; \
-    a.leafcp = leafcp_; a.gcp = gcp_; a.res = res_;                                   \
-    a.rank = L.doc_rank + w.first_doc; a.wg = nullptr;                                \
-    a.docs = L.docs_rel + w.first_doc;                                                \
-    a.text = text_;                                                                   \
-    a.text_cap = ord ? w.order_cap : cap_text_ - 64;                                  \
-    a.align = ord ? 1u : 16u;                                                         \
-    a.walk_text = 0;                                                                  \
-    a.rsh = 0;                                                                        \
-    a.sbytes = sbytes_;                                                               \
-    a.r_head = r_head_;                                                               \
-    a.chunk_doc = L.chunk_doc + (w.slot0 >> L.log2m);                                 \
-    a.log2c = L.log2m;                                                                \
-    a.wtmp = wtmp_;                                                                   \
-    a.ovf = ovf_
+template <>
+TreeArgs Engine::wave_args<TreeArgs>(const DeviceLogs& L, const Wave& w, bool ord) const {
+    TreeArgs a{};
+    a.ndocs = w.ndocs;
+    a.in_parent = r_parent_;
+    a.key = r_key_;
+    a.pstart = r_pstart_;
+    a.doc_root = doc_root_;
+    a.doc_p0 = doc_p0_;
+    a.rec = rec_; a.ctl = ctl_; a.swn = swn_;
+    a.roff = roff_;
+    a.rloc = rloc_;
+    a.tlen = tlen_; a.toff = toff_; a.loff = loff_; a.leafh = leafh_; a.ghash = ghash_;
+    a.leafcp = leafcp_; a.gcp = gcp_; a.res = res_;
+    a.rank = L.doc_rank + w.first_doc; a.wg = nullptr;
+    a.docs = L.docs_rel + w.first_doc;
+    a.text = text_;
+    a.text_cap = ord ? w.order_cap : text_room(cap_text_);
+    a.align = ord ? 1u : 16u;
+    a.walk_text = 0;
+    a.rsh = 0;
+    a.sbytes = sbytes_;
+    a.r_head = r_head_;
+    a.chunk_doc = L.chunk_doc + (w.slot0 >> L.log2m);
+    a.log2c = L.log2m;
+    a.wtmp = wtmp_;
+    a.ovf = ovf_;
+    return a;
+}
 
 // k_runs with 16, 32 or 64 slots per thread (Engine::runs_slots)
 void launch_k_runs(const L0Args& a0, uint32_t ntiles, hipStream_t s, uint32_t slots) {
@@ -4790,7 +4815,7 @@ void launch_k_runs(const L0Args& a0, uint32_t ntiles, hipStream_t s, uint32_t sl
 int Engine::launch_level0(DeviceLogs& L, const Wave& w, bool ord, bool copy_text,
                           uint32_t cap_runs, uint32_t cap_rmax, StageClock& ck) {
     hipStream_t s = cur_;
-    L0ARGS(a0);
+    L0Args a0 = wave_args<L0Args>(L, w, ord);
     a0.copy_text = copy_text ? 1u : 0u;
     a0.cap_runs = cap_runs;
     a0.cap_rmax = cap_rmax;
@@ -4825,7 +4850,7 @@ int Engine::launch_level0(DeviceLogs& L, const Wave& w, bool ord, bool copy_text
 
 // k_runs alone (run_wave: the run rows did not fit the rows allocated when level 0 ran).
 int Engine::launch_runs(DeviceLogs& L, const Wave& w, bool ord) {
-    L0ARGS(a0);
+    L0Args a0 = wave_args<L0Args>(L, w, ord);
     launch_k_runs(a0, a0.ntiles, cur_, runs_slots);
     HIPCHK(hipGetLastError(), "k_runs launch");
     return CRDT_HIP_OK;
@@ -4835,7 +4860,7 @@ int Engine::launch_runs(DeviceLogs& L, const Wave& w, bool ord) {
 int Engine::launch_lds_level1(DeviceLogs& L, const Wave& w, bool ord, const L1Plan& p,
                               bool stile, StageClock& ck) {
     hipStream_t s = cur_;
-    TREEARGS(a);
+    TreeArgs a = wave_args<TreeArgs>(L, w, ord);
     tail_nspl_ = 0;  // (k_doctree leaves any offsets k_expand needs in roff)
     const bool scatter = stile && p.scatter;
     tail_scatter_ = scatter;
@@ -4889,16 +4914,12 @@ int Engine::launch_lds_level1(DeviceLogs& L, const Wave& w, bool ord, const L1Pl
 int Engine::launch_global_level1(DeviceLogs& L, const Wave& w, bool ord, const L1Plan& p,
                                  StageClock& ck, uint32_t& rounds) {
     hipStream_t s = cur_;
-    TREEARGS(a);
+    TreeArgs a = wave_args<TreeArgs>(L, w, ord);
     tail_scatter_ = false;
-    const uint32_t R = p.R;
-    // splitter stride: longer sublists once the pointer jumping over the splitter lists
-    // dominates (measured on config 5: 182 M runs, stride 16 -> 64 took 72 -> 59 ms)
-    const uint32_t log2m_w = log2m_set ? this->log2m : (R > (1u << 24) ? 6u : 4u);
-    const uint32_t Sreg = 2 * ((R + (1u << log2m_w) - 1) >> log2m_w);
-    const uint32_t S = Sreg + w.ndocs;
+    // (the splitter geometry run_wave sized the scratch by)
+    const uint32_t R = p.R, Sreg = p.Sreg, S = p.S;
     a.R = R;
-    a.log2m = log2m_w;
+    a.log2m = p.log2m;
     a.Sreg = Sreg;
     a.S = S;
     a.step_limit = 2u * R + 4u;
@@ -5031,7 +5052,7 @@ int Engine::launch_global_level1(DeviceLogs& L, const Wave& w, bool ord, const L
     k_sup_init<<<gC, kBlock, 0, s>>>(sa);
     // a document's list holds at most 2 * (ceil(runs / M) + 1) + 1 splitters, of which at most
     // that / kSup + 2 are supers
-    rounds = ceil_log2((2ull * ((p.rmax + (1u << log2m_w) - 1) >> log2m_w) >> sa.slog2) + 8);
+    rounds = ceil_log2((2ull * ((p.rmax + (1u << p.log2m) - 1) >> p.log2m) >> sa.slog2) + 8);
     for (uint32_t k = 0; k < rounds; ++k)
         k_sup_step<<<gC, kBlock, 0, s>>>(svp_[k & 1], sa.Sc, svp_[(k + 1) & 1]);
     k_sup2<<<gC, kBlock, 0, s>>>(sa, svp_[rounds & 1]);
@@ -5055,8 +5076,8 @@ int Engine::launch_global_level1(DeviceLogs& L, const Wave& w, bool ord, const L
 int Engine::launch_tail(DeviceLogs& L, const Wave& w, bool ord, bool fused, StageClock& ck,
                         uint32_t* hblock) {
     hipStream_t s = cur_;
-    L0ARGS(a0);
-    TREEARGS(a);
+    L0Args a0 = wave_args<L0Args>(L, w, ord);
+    TreeArgs a = wave_args<TreeArgs>(L, w, ord);
     ExpandArgs ea{};
     ea.mode = a0.mode;
     ea.log2m = L.log2m;
@@ -5087,7 +5108,7 @@ int Engine::launch_tail(DeviceLogs& L, const Wave& w, bool ord, bool fused, Stag
         sa.roff = roff_;
         sa.stile = stile_;
         sa.text = text_;
-        sa.text_cap = cap_text_ - 64;
+        sa.text_cap = text_room(cap_text_);
         sa.ctl = ctl_;
         k_tscatter<<<grid_for(sa.ntiles, (kBlock / 64) * kScatterTiles), kBlock, 0, s>>>(sa);
         MARK(S_TEXT);
@@ -5106,7 +5127,6 @@ int Engine::launch_tail(DeviceLogs& L, const Wave& w, bool ord, bool fused, Stag
     return CRDT_HIP_OK;
 }
 #undef MARK
-#undef TREEARGS
 
 int Engine::finish_wave(const Wave& w, bool ord, bool static_l0, const L1Plan& p, uint32_t rounds,
                         const StageClock& ck, const uint32_t* hctl, std::vector<float>& stage_ms,
@@ -5148,15 +5168,7 @@ int Engine::run_wave(DeviceLogs& L, uint32_t wi, Mode mode, std::vector<float>& 
     const bool ord = mode == ORDER;
     StageClock ck{ev_.data(), 0, {}};
     uint32_t* hctl = host_block(L, wi);
-    // run records are written before the run count is known: runs <= slots (Fugue: rows <=
-    // 2 slots, a content and a tree row per head with left children)
-    const uint64_t hrows = w.nslots * (L.fugue ? 2ull : 1ull);
-    if (hrows > cap_heads_) {
-        dfree(r_head_); dfree(r_pstart_);
-        HIPCHK(dalloc(&r_head_, hrows + 64ull), "hipMalloc r_head");
-        HIPCHK(dalloc(&r_pstart_, hrows + 64ull), "hipMalloc r_pstart");
-        cap_heads_ = hrows;
-    }
+    if (const int hrc = ensure_heads(L, w)) return hrc;
     // ---- level 0: runs.  Lanes take turns here (an HBM stream): the gate is held from the first
     // level-0 launch to the level-0 sync, so one lane's level 0 overlaps the others' latency-bound
     // level 1.
@@ -5175,10 +5187,8 @@ int Engine::run_wave(DeviceLogs& L, uint32_t wi, Mode mode, std::vector<float>& 
     }
     L1Plan p = plan_level1(w, hctl[C_RTOTAL], hctl[C_RMAX], ord, force_global);
     p.scatter = false;  // (no stile here: k_runs writes the slot-order text, k_doctree stages it)
-    const uint32_t lg = log2m_set ? log2m : (p.R > (1u << 24) ? 6u : 4u);
-    const uint32_t Sreg = 2 * ((p.R + (1u << lg) - 1) >> lg);
     const uint64_t rows = cap_runs_;  // run rows k_runs could write
-    rc = ensure_runs(p.R, Sreg + w.ndocs);
+    rc = ensure_runs(p.R, p.S);
     if (rc) return rc;
     // sibling grouping of the global level 1: by counting when every document's runs stay within
     // a few MB (the atomics and gathers land in cache), else by the two radix sorts
@@ -5188,7 +5198,7 @@ int Engine::run_wave(DeviceLogs& L, uint32_t wi, Mode mode, std::vector<float>& 
     if (walk_text(w, ord, p)) {
         // a text slot per splitter of ~4x the mean sublist text (128 B .. 4 KiB; + slack for
         // k_tcopy's dword reads) and the overflow list
-        const uint64_t ns = (uint64_t)Sreg + w.ndocs;
+        const uint64_t ns = p.S;
         wtmp_log2_ = std::min<uint32_t>(12u, std::max<uint32_t>(
                          7u, ceil_log2(4ull * hctl[C_WTOTAL] / std::max<uint64_t>(1, ns) + 1)));
         if ((ns << wtmp_log2_) + 64 > cap_wtmp_) {
@@ -5273,6 +5283,46 @@ void Engine::collect(const DeviceLogs& L, uint32_t wi, uint64_t* digests, uint64
     }
 }
 
+void Engine::write_stats(crdt_hip_stats* st, const DeviceLogs& L, uint64_t text_bytes,
+                         uint64_t runs, const std::vector<float>* ms,
+                         const std::vector<uint32_t>* nl, uint32_t K, uint64_t total_ns) const {
+    std::memset(st, 0, sizeof *st);
+    st->items = L.items;
+    st->docs = (uint32_t)L.docs.size();
+    st->text_bytes = text_bytes;
+    st->runs = runs;
+    st->waves = (uint32_t)L.waves.size();
+    st->nstages = S_N;
+    for (int s = 0; s < S_N; ++s) {
+        double t = 0;
+        for (uint32_t i = 0; i < K; ++i) {
+            t += ms[i][s];
+            st->stage_launches[s] += nl[i][s];
+        }
+        st->stage_ns[s] = (uint64_t)(t * 1e6);
+    }
+    st->total_ns = total_ns;
+}
+
+int Engine::copy_text_out(const Wave& w, Mode mode, std::vector<uint8_t>* text_out,
+                          std::vector<uint64_t>* text_offsets) {
+    std::vector<uint64_t> offs(w.ndocs + 1);
+    HIPCHK(hipMemcpyAsync(offs.data(), toff_, (w.ndocs + 1) * 8ull, hipMemcpyDeviceToHost, stream),
+           "copy offsets");
+    HIPCHK(hipStreamSynchronize(stream), "copy offsets");
+    if (text_out) {
+        const uint64_t total = offs[w.ndocs] * (mode == ORDER ? 4 : 1);  // (ORDER: u32 entries)
+        text_out->resize(total);
+        if (total) {
+            HIPCHK(hipMemcpyAsync(text_out->data(), text_, total, hipMemcpyDeviceToHost, stream),
+                   "copy text");
+            HIPCHK(hipStreamSynchronize(stream), "copy text");
+        }
+    }
+    if (text_offsets) *text_offsets = offs;
+    return CRDT_HIP_OK;
+}
+
 int Engine::merge(DeviceLogs& L, Mode mode, uint64_t* digests, uint64_t* lens, crdt_hip_stats* st,
                   std::vector<uint8_t>* text_out, std::vector<uint64_t>* text_offsets,
                   uint64_t* cps) {
@@ -5314,26 +5364,11 @@ int Engine::merge_inner(DeviceLogs& L, Mode mode, uint64_t* digests, uint64_t* l
     if (hinted) {
         const int rc = merge_async(L, digests, lens, cps, st);
         if (rc || !want_text) return rc;
-        const Wave& w = L.waves[0];
-        std::vector<uint64_t> offs(w.ndocs + 1);
-        HIPCHK(hipMemcpyAsync(offs.data(), toff_, (w.ndocs + 1) * 8ull, hipMemcpyDeviceToHost, stream),
-               "copy offsets");
-        HIPCHK(hipStreamSynchronize(stream), "copy offsets");
-        if (text_out) {
-            text_out->resize(offs[w.ndocs]);
-            if (offs[w.ndocs]) {
-                HIPCHK(hipMemcpyAsync(text_out->data(), text_, offs[w.ndocs], hipMemcpyDeviceToHost,
-                                      stream), "copy text");
-                HIPCHK(hipStreamSynchronize(stream), "copy text");
-            }
-        }
-        if (text_offsets) *text_offsets = offs;
-        return CRDT_HIP_OK;
+        return copy_text_out(L.waves[0], mode, text_out, text_offsets);
     }
     if (lanes > 1 && L.waves.size() > 1 && !text_out) return merge_lanes(L, mode, digests, lens, cps, st);
     std::vector<float> stage_ms(S_N, 0.f);
     std::vector<uint32_t> stage_launches(S_N, 0);
-    const uint32_t ndocs = (uint32_t)L.docs.size();
     runs_ = 0;
     if (const int rc = ensure_host_out(L)) return rc;
     HIPCHK(hipEventRecord(ev_[2 * S_N + 1], stream), "event record");
@@ -5345,40 +5380,36 @@ int Engine::merge_inner(DeviceLogs& L, Mode mode, uint64_t* digests, uint64_t* l
         rc = run_wave(L, wi, mode, stage_ms, stage_launches);
         if (rc) return rc;
         collect(L, wi, digests, lens, cps, text_bytes);
-        if (text_out) {
-            std::vector<uint64_t> offs(w.ndocs + 1);
-            HIPCHK(hipMemcpyAsync(offs.data(), toff_, (w.ndocs + 1) * 8ull, hipMemcpyDeviceToHost,
-                                  stream), "copy offsets");
-            HIPCHK(hipStreamSynchronize(stream), "copy offsets");
-            const uint64_t total = offs[w.ndocs] * (mode == ORDER ? 4 : 1);
-            text_out->resize(total);
-            if (total) {
-                HIPCHK(hipMemcpyAsync(text_out->data(), text_, total, hipMemcpyDeviceToHost, stream),
-                       "copy text");
-                HIPCHK(hipStreamSynchronize(stream), "copy text");
-            }
-            if (text_offsets) *text_offsets = offs;
-        }
+        if (text_out && (rc = copy_text_out(w, mode, text_out, text_offsets))) return rc;
     }
     HIPCHK(hipEventRecord(ev_[2 * S_N + 2], stream), "event record");
     HIPCHK(hipEventSynchronize(ev_[2 * S_N + 2]), "event sync");
     if (st) {
-        std::memset(st, 0, sizeof *st);
-        st->items = L.items;
-        st->docs = ndocs;
-        st->text_bytes = text_bytes;
-        st->runs = runs_;
-        st->waves = (uint32_t)L.waves.size();
-        st->nstages = S_N;
-        for (int i = 0; i < S_N; ++i) {
-            st->stage_ns[i] = (uint64_t)((double)stage_ms[i] * 1e6);
-            st->stage_launches[i] = stage_launches[i];
-        }
         float tot = 0;
         HIPCHK(hipEventElapsedTime(&tot, ev_[2 * S_N + 1], ev_[2 * S_N + 2]), "event time");
-        st->total_ns = (uint64_t)((double)tot * 1e6);
+        write_stats(st, L, text_bytes, runs_, &stage_ms, &stage_launches, 1,
+                    (uint64_t)((double)tot * 1e6));
     }
     return CRDT_HIP_OK;
+}
+
+std::vector<Engine*> Engine::lane_engines(uint32_t K) {
+    while (lane_eng_.size() + 1 < K) {
+        auto e = std::make_unique<Engine>();
+        const std::string msg = e->init(device);
+        if (!msg.empty()) {
+            err = "lane engine: " + msg;
+            return {};
+        }
+        lane_eng_.push_back(std::move(e));
+    }
+    std::vector<Engine*> eng(K, this);
+    for (uint32_t i = 1; i < K; ++i) {
+        eng[i] = lane_eng_[i - 1].get();
+        static_cast<Tunables&>(*eng[i]) = *this;
+        eng[i]->probe_doc_ = probe_doc_;
+    }
+    return eng;
 }
 
 // Every wave of a merge whose launch plans are known (an earlier merge of the same logs, or of
@@ -5395,33 +5426,8 @@ int Engine::merge_async_prepare(DeviceLogs& L, AsyncMerge& m, bool timed) {
     const uint32_t nw = (uint32_t)L.waves.size();
     m.K = std::max<uint32_t>(1, std::min<uint32_t>(lanes, nw));
     m.timed = timed;
-    while (lane_eng_.size() + 1 < m.K) {
-        auto e = std::make_unique<Engine>();
-        const std::string msg = e->init(device);
-        if (!msg.empty()) {
-            err = "lane engine: " + msg;
-            return CRDT_HIP_EDEVICE;
-        }
-        lane_eng_.push_back(std::move(e));
-    }
-    m.eng.assign(m.K, this);
-    for (uint32_t i = 1; i < m.K; ++i) {
-        m.eng[i] = lane_eng_[i - 1].get();
-        m.eng[i]->log2m = log2m;
-        m.eng[i]->log2m_set = log2m_set;
-        m.eng[i]->level1_global = level1_global;
-        m.eng[i]->fuse_text = fuse_text;
-        m.eng[i]->xcd_order = xcd_order;
-        m.eng[i]->stile_text = stile_text;
-        m.eng[i]->text_scatter = text_scatter;
-        m.eng[i]->glds_late = glds_late;
-        m.eng[i]->doctree_k32 = doctree_k32;
-        m.eng[i]->runs_slots = runs_slots;
-        m.eng[i]->static_jumps = static_jumps;
-        m.eng[i]->dead_skip = dead_skip;
-        m.eng[i]->l1_split = l1_split;
-        m.eng[i]->probe_doc_ = probe_doc_;
-    }
+    m.eng = lane_engines(m.K);
+    if (m.eng.empty()) return CRDT_HIP_EDEVICE;
     // every allocation before the first launch (a pool free waits for the device)
     const uint32_t per_lane = (nw + m.K - 1) / m.K;
     m.plans.assign(nw, L1Plan{});
@@ -5436,14 +5442,8 @@ int Engine::merge_async_prepare(DeviceLogs& L, AsyncMerge& m, bool timed) {
         if (rc) return rc;
         rc = E.ensure_runs(cr, 0);
         if (rc) return rc;
-        const uint64_t hrows = w.nslots * (L.fugue ? 2ull : 1ull);  // (see run_wave)
-        if (hrows > E.cap_heads_) {
-            dfree(E.r_head_); dfree(E.r_pstart_);
-            HIPCHK(dalloc(&E.r_head_, hrows + 64ull), "hipMalloc r_head");
-            HIPCHK(dalloc(&E.r_pstart_, hrows + 64ull), "hipMalloc r_pstart");
-            E.cap_heads_ = hrows;
-            E.gen_++;
-        }
+        rc = E.ensure_heads(L, w);
+        if (rc) return rc;
     }
     for (uint32_t i = 0; i < m.K; ++i) {
         int rc = m.eng[i]->ensure_host_out(L);
@@ -5515,7 +5515,6 @@ int Engine::merge_async_enqueue(DeviceLogs& L, AsyncMerge& m) {
 int Engine::merge_async_finish(DeviceLogs& L, AsyncMerge& m, uint64_t* digests, uint64_t* lens,
                                uint64_t* cps, crdt_hip_stats* st) {
     const uint32_t nw = (uint32_t)L.waves.size();
-    const uint32_t ndocs = (uint32_t)L.docs.size();
     std::vector<float> stage_ms(S_N, 0.f);
     std::vector<uint32_t> stage_launches(S_N, 0);
     uint64_t text_bytes = 0, runs = 0;
@@ -5560,22 +5559,11 @@ int Engine::merge_async_finish(DeviceLogs& L, AsyncMerge& m, uint64_t* digests, 
     }
     runs_ = runs;
     if (st) {
-        std::memset(st, 0, sizeof *st);
-        st->items = L.items;
-        st->docs = ndocs;
-        st->text_bytes = text_bytes;
-        st->runs = runs;
-        st->waves = nw;
-        st->nstages = S_N;
-        for (int i = 0; i < S_N; ++i) {
-            st->stage_ns[i] = (uint64_t)((double)stage_ms[i] * 1e6);
-            st->stage_launches[i] = stage_launches[i];
-        }
-        if (m.timed) {
-            float tot = 0;
+        float tot = 0;
+        if (m.timed)
             HIPCHK(hipEventElapsedTime(&tot, ev_[2 * S_N + 1], ev_[2 * S_N + 2]), "event time");
-            st->total_ns = (uint64_t)((double)tot * 1e6);
-        }
+        write_stats(st, L, text_bytes, runs, &stage_ms, &stage_launches, 1,
+                    (uint64_t)((double)tot * 1e6));
     }
     return CRDT_HIP_OK;
 }
@@ -5601,33 +5589,9 @@ int Engine::merge_lanes(DeviceLogs& L, Mode mode, uint64_t* digests, uint64_t* l
     const uint32_t K = std::min<uint32_t>(lanes, nw);
     // the lanes' streams do not wait for this one: let its queued table uploads finish
     HIPCHK(hipStreamSynchronize(stream), "table sync");
-    while (lane_eng_.size() + 1 < K) {
-        auto e = std::make_unique<Engine>();
-        const std::string m = e->init(device);
-        if (!m.empty()) {
-            err = "lane engine: " + m;
-            return CRDT_HIP_EDEVICE;
-        }
-        lane_eng_.push_back(std::move(e));
-    }
-    std::vector<Engine*> eng(K, this);
+    const std::vector<Engine*> eng = lane_engines(K);
+    if (eng.empty()) return CRDT_HIP_EDEVICE;
     std::mutex gate;
-    for (uint32_t i = 1; i < K; ++i) {
-        eng[i] = lane_eng_[i - 1].get();
-        eng[i]->log2m = log2m;
-        eng[i]->log2m_set = log2m_set;
-        eng[i]->level1_global = level1_global;
-        eng[i]->fuse_text = fuse_text;
-        eng[i]->xcd_order = xcd_order;
-        eng[i]->stile_text = stile_text;
-        eng[i]->text_scatter = text_scatter;
-        eng[i]->glds_late = glds_late;
-        eng[i]->doctree_k32 = doctree_k32;
-        eng[i]->runs_slots = runs_slots;
-        eng[i]->static_jumps = static_jumps;
-        eng[i]->dead_skip = dead_skip;
-        eng[i]->probe_doc_ = probe_doc_;
-    }
     std::vector<int> rc(K, CRDT_HIP_OK);
     std::vector<std::vector<float>> ms(K, std::vector<float>(S_N, 0.f));
     std::vector<std::vector<uint32_t>> nl(K, std::vector<uint32_t>(S_N, 0));
@@ -5661,31 +5625,11 @@ int Engine::merge_lanes(DeviceLogs& L, Mode mode, uint64_t* digests, uint64_t* l
             if (i) err = eng[i]->err;
             return rc[i];
         }
-    const uint32_t ndocs = (uint32_t)L.docs.size();
     uint64_t text_bytes = 0, runs = 0;
     for (uint32_t wi = 0; wi < nw; ++wi) eng[wi % K]->collect(L, wi, digests, lens, cps, text_bytes);
     for (uint32_t i = 0; i < K; ++i) runs += eng[i]->runs_;
     runs_ = runs;
-    if (st) {
-        std::memset(st, 0, sizeof *st);
-        st->items = L.items;
-        st->docs = ndocs;
-        st->text_bytes = text_bytes;
-        st->runs = runs;
-        st->waves = nw;
-        st->nstages = S_N;
-        for (int s = 0; s < S_N; ++s) {
-            double t = 0;
-            uint32_t n = 0;
-            for (uint32_t i = 0; i < K; ++i) {
-                t += ms[i][s];
-                n += nl[i][s];
-            }
-            st->stage_ns[s] = (uint64_t)(t * 1e6);
-            st->stage_launches[s] = n;
-        }
-        st->total_ns = (uint64_t)wall_ns;
-    }
+    if (st) write_stats(st, L, text_bytes, runs, ms.data(), nl.data(), K, (uint64_t)wall_ns);
     return CRDT_HIP_OK;
 }
 
@@ -5854,12 +5798,12 @@ int Engine::nsq_reserve_prefix(DeviceLogs& L) {
 
 // Counts of the nsq items per 64-slot chunk, scanned in place into L.nsq_pre (launches only).
 void Engine::nsq_count_scan(DeviceLogs& L) {
-    const bool ord = false;  // (L0ARGS)
-    L.tomb_ok = false;       // (before L0ARGS: the launches below are not on the plane path)
+    // (before the wave's arguments: the launches below are not on the plane path)
+    L.tomb_ok = false;
     const uint32_t n = (uint32_t)(L.total_slots / 64 + 64);
     (void)hipMemsetAsync(L.nsq_pre, 0, (n + 1ull) * 4, stream);
     for (const Wave& w : L.waves) {
-        L0ARGS(a0);
+        const L0Args a0 = wave_args<L0Args>(L, w, false);
         k_nsq_count<<<grid_for((w.nslots + 15) / 16), kBlock, 0, stream>>>(
             a0, L.nsq_pre + (w.slot0 >> 6), L.nsq_mask + (w.slot0 >> 6),
             L.tomb ? L.tomb + (w.slot0 >> 6) : nullptr);
@@ -5978,9 +5922,8 @@ int Engine::raw_keep(DeviceLogs& L) {
     HIPCHK(dalloc(&L.raw_agent, n), "hipMalloc raw agent");
     HIPCHK(dalloc(&L.raw_del, n), "hipMalloc raw deleted");
     HIPCHK(dalloc(&L.raw_cp, n), "hipMalloc raw codepoint");
-    const bool ord = false;  // (L0ARGS)
     for (const Wave& w : L.waves) {
-        L0ARGS(a0);
+        const L0Args a0 = wave_args<L0Args>(L, w, false);
         k_raw_fill<<<grid_for(w.nslots), kBlock, 0, stream>>>(a0, L.raw_lam + w.slot0,
                                                                L.raw_agent + w.slot0,
                                                                L.raw_del + w.slot0,
@@ -5996,12 +5939,11 @@ int Engine::raw_keep(DeviceLogs& L) {
 // The merge's input encoding from the raw columns (launches only, on the engine's stream): keys,
 // codepoint words and nsq counts per wave, then the nsq scan and list (when the batch keeps one).
 int Engine::raw_encode(DeviceLogs& L) {
-    const bool ord = false;  // (L0ARGS)
     const bool nsq = L.nsq_ok && L.nsq_pre;
-    L.tomb_ok = false;  // (before L0ARGS: the codepoint words are rewritten below)
+    L.tomb_ok = false;  // (before the wave's arguments: the codepoint words are rewritten below)
     if (nsq) (void)hipMemsetAsync(L.nsq_pre, 0, (L.total_slots / 64 + 65) * 4ull, stream);
     for (const Wave& w : L.waves) {
-        L0ARGS(a0);
+        const L0Args a0 = wave_args<L0Args>(L, w, false);
         k_raw_encode<<<grid_for((w.nslots + 3) / 4), kBlock, 0, stream>>>(
             a0, L.raw_lam + w.slot0, L.raw_agent + w.slot0, L.raw_del + w.slot0,
             L.raw_cp + w.slot0, L.key + w.slot0, L.cp + 3ull * w.slot0,
@@ -6020,13 +5962,13 @@ int Engine::raw_encode(DeviceLogs& L) {
 // The list itself, every wave's tiles (launches only), and with it the static jump bits of RGA
 // logs (DeviceLogs::jump): zeroed with their flag, then set by the same launches.
 void Engine::nsq_scatter(DeviceLogs& L) {
-    const bool ord = false;  // (L0ARGS)
     const uint64_t jw = DeviceLogs::kJumpHead + jbits_words(L.total_slots);
     const bool sj = static_jumps && !L.fugue && L.jump && L.jump_cap >= jw;
-    L.jump_ok = false;  // (before L0ARGS: the launches below are not on the static path)
+    // (before the wave's arguments: the launches below are not on the static path)
+    L.jump_ok = false;
     if (sj) (void)hipMemsetAsync(L.jump, 0, jw * 4ull, stream);
     for (const Wave& w : L.waves) {
-        L0ARGS(a0);
+        const L0Args a0 = wave_args<L0Args>(L, w, false);
         k_nsq_scatter<<<(uint32_t)((w.nslots + kScanTile - 1) / kScanTile), kBlock, 0, stream>>>(
             a0, L.nsq_pre + (w.slot0 >> 6), L.nsq_mask + (w.slot0 >> 6), L.nsq_par, L.nsq_key,
             sj ? L.jump + DeviceLogs::kJumpHead + (w.slot0 >> 5) : nullptr, L.jump);

@@ -9,9 +9,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "crdt_hip.h"
@@ -70,6 +72,9 @@ struct L1Plan {
     bool scatter = false;
     uint32_t rcap = 0, scap = 0;
     uint64_t dyn_bytes = 0, dyn_scatter = 0;
+    // splitters of the global level 1: stride 2^log2m, Sreg regular ones, S with one per document
+    // (run_wave sizes the splitter scratch by them, launch_global_level1 indexes it by them)
+    uint32_t log2m = 4, Sreg = 0, S = 0;
 };
 
 // The codepoint column: 3 bytes per slot, the codepoint (bits 0-20), the tombstone flag (bit 23)
@@ -164,7 +169,83 @@ struct DeviceLogs {
     ~DeviceLogs() { release(); }
 };
 
-class Engine {
+// The caller-settable knobs of an engine (crdt_hip_set_param; capi.cpp's kParams gives each its
+// ABI name, accepted values and message).  Every knob is a uint64_t, the ABI's value type, so that
+// a table row names its field, a lane engine takes the block by one assignment
+// (Engine::lane_engines) and the block as words keys a captured replay (replica_replay).
+struct Tunables {
+    uint64_t log2m = 4;      // level-1 splitter stride M = 2^log2m
+    uint64_t log2m_set = 0;  // set by the caller; else chosen per wave from R
+    uint64_t max_wave_slots = 1ull << 30;
+    // last wave of a multi-wave merge <= max / div (0: off; off since the dead-run drop and the
+    // smaller k_doctree: 12.37 -> 12.09 ms at the headline config, tools/sweep_sched.sh)
+    uint64_t tail_wave_div = 0;
+    uint64_t level1_global = 0;  // never use the per-document LDS level 1
+    // Waves merged at once by a multi-wave merge, each on a lane of its own: a helper engine
+    // (non-blocking stream + scratch) driven by its own host thread.  The latency-bound level 1
+    // of one wave then overlaps the HBM-bound level 0 of another.
+    uint64_t lanes = 2;
+    uint64_t l0_gated = 1;  // lanes take turns at level 0 (see run_wave)
+    // Enqueued waves (merge_async) run level 1 and the tail on stream_l1, created with the lowest
+    // stream priority, so that when one wave's latency-bound level 1 and the next wave's HBM-bound
+    // level 0 compete for the CUs, the dispatcher favours level 0 (the chain that bounds a merge).
+    // (off by default since the round-2 level-0 work: 12.09 -> 12.05 ms, within noise; the
+    // parameter stays for the A/B)
+    uint64_t l1_split = 0;
+    // Merges of logs merged before enqueue every wave with its learnt plan and wait once at the
+    // end (merge_async) instead of after each wave's level 0.
+    uint64_t plan_cache = 1;
+    uint64_t plan_shrink = 0;  // test hook: enqueue with half the learnt plan (forces C_REPLAN)
+    uint64_t doctree_lds_max = 0;  // experiment hook: k_doctree always takes the whole LDS
+    uint64_t fuse_text = 1;        // k_doctree writes the text when it fits LDS (else k_expand)
+    // the compact list of the non-seq items' parents and keys: 1 = resident batches (build_nsq)
+    // and replicas of at least kNsqReplicaSlots slots (rebuilt by every merge: below that size
+    // the rebuild's launches cost more than the gathers it saves, measured on the downstream
+    // closures, DESIGN.md §6), 2 = every replica too, 0 = never (level 0 gathers the columns)
+    uint64_t nsq_list = 1;
+    // 1: RGA logs with a list keep their jump bits resident (DeviceLogs::jump) and level 0 takes
+    // the static path on contracted waves: k_clear clears ctl only, k_classify sets no jump bits
+    // and computes the run heads of its tile itself (no k_heads launch); 0: every merge rebuilds
+    // the bits in k_classify and runs k_heads
+    uint64_t static_jumps = 1;
+    // 1: TEXT merges of waves on the static path take the plane form of k_classify
+    // (k_classify_plane): tombstones and nsq flags from the resident bit planes
+    // (DeviceLogs::tomb, nsq_mask), the codepoint words only of 16-slot groups that hold a
+    // visible item; nsqb is not written, k_runs reads the resident nsq plane.  0: k_classify
+    // reads the codepoint word of every slot.
+    uint64_t dead_skip = 1;
+    // run contraction of RGA waves: 0 = by the wave's input (no contraction when at least
+    // kNoconShare of its items lack the previous-slot flag), 1 = always, 2 = never
+    uint64_t contraction = 0;
+    // sibling grouping of the global level 1: 0 = by the largest document (counting up to
+    // kCsrDocRuns runs, else radix sorts), 1 = always counting, 2 = always radix sorts
+    uint64_t l1_group = 0;
+    uint64_t rs_digit_bits = 0;  // sort A's digit width: 0 = 10 bits where that saves a pass, else 8
+    uint64_t xcd_order = 1;  // XCD-aware tile order in k_classify / k_runs (engine.hip xcd_block)
+    // fused plans stage text from the tile segments (L1Plan::stile_text): 1 by 16-byte loads and
+    // funnel shifts into one contiguous image, 2 by LDS-DMA, tile by tile (engine.hip stage_glds)
+    uint64_t stile_text = 2;
+    // 1: stile plans leave the text to k_tscatter (L1Plan::scatter); 0: k_doctree phase C (the
+    // default: the two measured equal on the RGA headline, 8.43 ms per step either way, and
+    // phase C is 0.16 ms faster on the Fugue line; DESIGN.md §5)
+    uint64_t text_scatter = 0;
+    uint64_t glds_late = 0;  // test hook: k_doctree issues its LDS-DMA staging loads last
+    // every LDS level 1 on k_doctree_wide (32-bit keys, 9 B of LDS per run instead of 15)
+    uint64_t doctree_k32 = 0;
+    // k_runs slots per thread: 16 (256 threads per tile), 32 (128) or 64 (one wave per tile,
+    // 64-bit slot masks)
+    uint64_t runs_slots = 32;
+    uint64_t group_docs = 0;  // replicate(): documents in slots base by base (waves per base)
+    // every knob as a word
+    std::vector<uint64_t> words() const {
+        std::vector<uint64_t> v(sizeof *this / sizeof(uint64_t));
+        std::memcpy(v.data(), this, sizeof *this);
+        return v;
+    }
+};
+static_assert(std::has_unique_object_representations_v<Tunables>, "words() needs a block of words");
+
+class Engine : public Tunables {
 public:
     Engine() = default;
     ~Engine();
@@ -173,60 +254,13 @@ public:
     int device = 0;
     hipStream_t stream = nullptr;     // every launch of the engine (high priority)
     hipStream_t stream_l1 = nullptr;  // level 1 + tail of enqueued waves (low priority: l1_split)
-    uint32_t log2m = 4;                    // level-1 splitter stride M = 2^log2m
-    bool log2m_set = false;                // set by the caller; else chosen per wave from R
-    uint64_t max_wave_slots = 1ull << 30;
-    // last wave of a multi-wave merge <= max / div (0: off; off since the dead-run drop and the
-    // smaller k_doctree: 12.37 -> 12.09 ms at the headline config, tools/sweep_sched.sh)
-    uint32_t tail_wave_div = 0;
-    bool level1_global = false;            // never use the per-document LDS level 1
-    // Waves merged at once by a multi-wave merge, each on a lane of its own: a helper engine
-    // (non-blocking stream + scratch) driven by its own host thread.  The latency-bound level 1
-    // of one wave then overlaps the HBM-bound level 0 of another.
-    uint32_t lanes = 2;
-    bool l0_gated = true;  // lanes take turns at level 0 (see run_wave)
-    // Enqueued waves (merge_async) run level 1 and the tail on stream_l1, created with the lowest
-    // stream priority, so that when one wave's latency-bound level 1 and the next wave's HBM-bound
-    // level 0 compete for the CUs, the dispatcher favours level 0 (the chain that bounds a merge).
-    // (off by default since the round-2 level-0 work: 12.09 -> 12.05 ms, within noise; the
-    // parameter stays for the A/B)
-    bool l1_split = false;
-    // Merges of logs merged before enqueue every wave with its learnt plan and wait once at the
-    // end (merge_async) instead of after each wave's level 0.
-    bool plan_cache = true;
-    bool plan_shrink = false;  // test hook: enqueue with half the learnt plan (forces C_REPLAN)
-    bool doctree_lds_max = false;  // experiment hook: k_doctree always takes the whole LDS
-    bool fuse_text = true;         // k_doctree writes the text when it fits LDS (else k_expand)
-    // the compact list of the non-seq items' parents and keys: 1 = resident batches (build_nsq)
-    // and replicas of at least kNsqReplicaSlots slots (rebuilt by every merge: below that size
-    // the rebuild's launches cost more than the gathers it saves, measured on the downstream
-    // closures, DESIGN.md §6), 2 = every replica too, 0 = never (level 0 gathers the columns)
-    uint32_t nsq_list = 1;
-    // 1: RGA logs with a list keep their jump bits resident (DeviceLogs::jump) and level 0 takes
-    // the static path on contracted waves: k_clear clears ctl only, k_classify sets no jump bits
-    // and computes the run heads of its tile itself (no k_heads launch); 0: every merge rebuilds
-    // the bits in k_classify and runs k_heads
-    uint32_t static_jumps = 1;
     bool static_wave(const DeviceLogs& L, const Wave& w) const {
         return static_jumps && L.nsq_ok && L.jump && L.jump_ok && !L.fugue && !w.nocon;
     }
-    // 1: TEXT merges of waves on the static path take the plane form of k_classify
-    // (k_classify_plane): tombstones and nsq flags from the resident bit planes
-    // (DeviceLogs::tomb, nsq_mask), the codepoint words only of 16-slot groups that hold a
-    // visible item; nsqb is not written, k_runs reads the resident nsq plane.  0: k_classify
-    // reads the codepoint word of every slot.
-    uint32_t dead_skip = 1;
     bool plane_wave(const DeviceLogs& L, const Wave& w, bool ord) const {
         return dead_skip && !ord && static_wave(L, w) && L.tomb && L.tomb_ok;
     }
     static constexpr uint64_t kNsqReplicaSlots = 1ull << 22;
-    // run contraction of RGA waves: 0 = by the wave's input (no contraction when at least
-    // kNoconShare of its items lack the previous-slot flag), 1 = always, 2 = never
-    uint32_t contraction = 0;
-    // sibling grouping of the global level 1: 0 = by the largest document (counting up to
-    // kCsrDocRuns runs, else radix sorts), 1 = always counting, 2 = always radix sorts
-    uint32_t l1_group = 0;
-    uint32_t rs_digit_bits = 0;  // sort A's digit width: 0 = 10 bits where that saves a pass, else 8
     std::string err;
     // err = "<what>: <the HIP error>", the sticky HIP error cleared; returns CRDT_HIP_EDEVICE
     int fail(const char* what, hipError_t e);
@@ -273,21 +307,6 @@ public:
                            uint64_t* cps, crdt_hip_stats* st);
     // bumped by every (re)allocation of scratch, this engine's or a lane engine's (a graph that
     // captured a multi-lane merge holds the lane engines' pointers too)
-    bool xcd_order = true;  // XCD-aware tile order in k_classify / k_runs (engine.hip xcd_block)
-    // fused plans stage text from the tile segments (L1Plan::stile_text): 1 by 16-byte loads and
-    // funnel shifts into one contiguous image, 2 by LDS-DMA, tile by tile (engine.hip stage_glds)
-    uint32_t stile_text = 2;
-    // 1: stile plans leave the text to k_tscatter (L1Plan::scatter); 0: k_doctree phase C (the
-    // default: the two measured equal on the RGA headline, 8.43 ms per step either way, and
-    // phase C is 0.16 ms faster on the Fugue line; DESIGN.md §5)
-    uint32_t text_scatter = 0;
-    bool glds_late = false;  // test hook: k_doctree issues its LDS-DMA staging loads last
-    // every LDS level 1 on k_doctree_wide (32-bit keys, 9 B of LDS per run instead of 15)
-    bool doctree_k32 = false;
-    // k_runs slots per thread: 16 (256 threads per tile), 32 (128) or 64 (one wave per tile,
-    // 64-bit slot masks)
-    uint32_t runs_slots = 32;
-    bool group_docs = false;  // replicate(): documents in slots base by base (waves per base)
     uint64_t generation() const {
         uint64_t g = gen_;
         for (const auto& e : lane_eng_) g += e->generation() + 1;
@@ -423,10 +442,14 @@ private:
     uint32_t* tab_local_ = nullptr;
     uint64_t cap_tab_ = 0;
 
+    // Lanes 0..K-1 of a multi-wave merge: this engine, then the lane engines (created when
+    // missing), each with this engine's tunables.  Empty: a lane engine failed to start (err).
+    std::vector<Engine*> lane_engines(uint32_t K);
     int merge_lanes(DeviceLogs& L, Mode mode, uint64_t* digests, uint64_t* lens, uint64_t* cps,
                     crdt_hip_stats* st);
     int merge_async(DeviceLogs& L, uint64_t* digests, uint64_t* lens, uint64_t* cps,
                     crdt_hip_stats* st);
+    int ensure_heads(const DeviceLogs& L, const Wave& w);
     int ensure_runs(uint64_t runs, uint64_t splitters);
     int ensure_radix(uint64_t runs);
     int ensure_csr(uint64_t runs);
@@ -444,6 +467,13 @@ private:
         return !p.lds1 && !ord && w.nocon;
     }
     int clock_mark(StageClock& c, int stage);
+    // The argument blocks of a wave's launches, filled from L and this engine's scratch
+    // (engine.hip: Args is L0Args or TreeArgs, types local to that file).
+    template <class Args>
+    Args wave_args(const DeviceLogs& L, const Wave& w, bool ord) const;
+    // What the kernels may write of a text buffer of `cap` bytes: all but the 64 bytes of slack
+    // behind it (0 for a buffer never grown: the kernels' store guards then refuse every store).
+    static uint64_t text_room(uint64_t cap) { return cap > 64 ? cap - 64 : 0; }
     // The launches of one wave, in stream order.
     int launch_runs(DeviceLogs& L, const Wave& w, bool ord);
     int launch_level0(DeviceLogs& L, const Wave& w, bool ord, bool copy_text, uint32_t cap_runs,
@@ -465,6 +495,13 @@ private:
                  std::vector<uint32_t>& stage_launches, bool force_global = false);
     void collect(const DeviceLogs& L, uint32_t wi, uint64_t* digests, uint64_t* lens,
                  uint64_t* cps, uint64_t& text_bytes) const;
+    // The stats block of a merge; stage times and launch counts summed over K lanes' arrays.
+    void write_stats(crdt_hip_stats* st, const DeviceLogs& L, uint64_t text_bytes, uint64_t runs,
+                     const std::vector<float>* ms, const std::vector<uint32_t>* nl, uint32_t K,
+                     uint64_t total_ns) const;
+    // Offsets and text of the one wave this engine merged last, copied to the host.
+    int copy_text_out(const Wave& w, Mode mode, std::vector<uint8_t>* text_out,
+                      std::vector<uint64_t>* text_offsets);
 };
 
 // In a function that returns a CRDT_HIP_* code: a HIP error ends it through E.fail.

@@ -740,15 +740,11 @@ int replica_replay(Engine& E, const Replica& init, const UpdateBatch& ub, Replay
             Engine::AsyncMerge m;
             rc = E.merge_async_prepare(w.logs, m, false);
             if (rc) return rc;
-            const std::vector<uint64_t> key = {
-                E.generation(), w.gen, init.gen, (uint64_t)(uintptr_t)&init, init.n, init.vis_bytes,
-                cap, (uint64_t)(uintptr_t)&ub, ub.len, ub.n, st.n_after, b_plan,
-                // (knobs that change what is captured: a closure captured under other settings
-                // is not replayed)
-                (uint64_t)E.nsq_list, (uint64_t)E.contraction, (uint64_t)E.runs_slots,
-                (uint64_t)E.stile_text, (uint64_t)E.xcd_order, (uint64_t)E.text_scatter,
-                (uint64_t)E.fuse_text, (uint64_t)E.lanes, (uint64_t)E.static_jumps,
-                (uint64_t)E.dead_skip};
+            // (every tunable: a closure captured under other settings is not replayed)
+            std::vector<uint64_t> key = E.words();
+            key.insert(key.end(), {E.generation(), w.gen, init.gen, (uint64_t)(uintptr_t)&init,
+                                   init.n, init.vis_bytes, cap, (uint64_t)(uintptr_t)&ub, ub.len,
+                                   ub.n, st.n_after, b_plan});
             hipStream_t s = E.stream;
             if (key != st.key || !st.exec) {
                 drop_graph(st);

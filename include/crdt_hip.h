@@ -164,7 +164,7 @@ int crdt_hip_init(int device, crdt_hip_ctx** out);
 int crdt_hip_destroy(crdt_hip_ctx* ctx);
 const char* crdt_hip_last_error(const crdt_hip_ctx* ctx);
 /* Tuning: "splitter_stride" of the global list ranking (power of two, 16..4096; default 16),
- * "max_wave_slots" per device wave (default 2^30), and "level1": 0 = per-document LDS merge of
+ * "max_wave_slots" per device wave (4096..2^31, default 2^30), and "level1": 0 = per-document LDS merge of
  * the run tree whenever every document of a wave fits a workgroup's LDS (default), 1 = always
  * the global (multi-kernel) level-1 path, and "lanes" (1..8, default 2): waves of a multi-wave
  * merge run concurrently on that many streams, each with its own scratch (1 = one after the
@@ -173,7 +173,7 @@ const char* crdt_hip_last_error(const crdt_hip_ctx* ctx);
  * merge learnt, checked on the device, and waits once instead of after each wave's level 0),
  * "l1_split" (default 0; 1: such enqueued waves run level 1 on a low-priority stream of their
  * lane, so that the next wave's level 0 is favoured when the two compete for the CUs),
- * "tail_wave_div" (default 0; k: a merge of several waves ends with a wave of at most
+ * "tail_wave_div" (0..64, default 0; k: a merge of several waves ends with a wave of at most
  * max_wave_slots / k slots), "xcd_order" (default 1: XCD-aware tile order in level 0),
  * "group_docs" (replica batches: 1 = documents placed in slots base by base, each base's
  * replicas in waves of their own, so that only the waves of a base whose run trees exceed the
@@ -198,8 +198,11 @@ const char* crdt_hip_last_error(const crdt_hip_ctx* ctx);
  * at most 2^16 runs or the wave at most 2^23, else by radix sorts (default), 1 = always
  * counting, 2 = always radix sorts), "rs_digit_bits" (digit width of the radix sort by parent:
  * 0 = 10 bits where that takes fewer passes than 8 (default), 8, 10),
- * "fuse_text"
- * (default 1).  Results never depend on these. */
+ * "text_scatter" (default 0; 1: the text of such plans is written by a kernel of its own after the
+ * per-document merge), "doctree_k32" (default 0; 1: every per-document merge on 32-bit sibling
+ * keys).  A value outside a parameter's range is CRDT_HIP_EINVAL; the switches take 0 or 1.
+ * Hooks for tests and experiments, any value, nonzero = on: "fuse_text" (default 1),
+ * "doctree_lds_max", "glds_late", "plan_shrink" (default 0).  Results never depend on these. */
 int crdt_hip_set_param(crdt_hip_ctx* ctx, const char* key, uint64_t value);
 
 /* ---- op log: host-side resolver (positional patch -> anchor op) ---------------------------- */

@@ -689,6 +689,76 @@ def test_uncontracted_uploads_match_oracle_and_reject_bad_parents(oracle, level1
     c.close()
 
 
+@pytest.mark.parametrize("group,scans", [(2, 1), (1, 3)])
+def test_tunables_reach_every_lane(oracle, group, scans):
+    """A multi-wave merge on two lanes: the lane engine groups siblings as the caller set it.
+    Four logs of 3,008 slots under max_wave_slots 4096 are four waves, two per lane, on the
+    global level 1; the radix grouping launches one scan per wave and the counting one three
+    (documents this small take the counting one by default), so the scan count tells what every
+    lane ran."""
+    c = crdt_hip.Context(0)
+    c.set_param("level1", 1)
+    c.set_param("lanes", 2)
+    c.set_param("max_wave_slots", 4096)
+    c.set_param("l1_group", group)
+    logs = [crdt_hip.OpLog.synth_agents(3000, 4, 0x5EED0100 + i).arrays() for i in range(4)]
+    dig, lens, st = c.merge_batch(logs, stats=True)
+    c.close()
+    assert st["waves"] == 4
+    assert st["stage_launches"]["scan"] == scans * st["waves"]
+    for i, lg in enumerate(logs):
+        ref = oracle.merge(to_anchor(lg))
+        assert lens[i] == len(ref), i
+        assert dig[i] == oracle.tree_digest(ref), i
+
+
+# crdt_hip_set_param as include/crdt_hip.h and INTEGRATION.md document it: the name, the smallest
+# and the largest accepted value, values that are refused, and the message for those.  (The hooks
+# at the end take any value.)
+_PARAM_DOC = [
+    ("splitter_stride", 16, 4096, [8, 48, 4097, 8192],
+     "splitter_stride must be a power of two in [16, 4096]"),
+    ("max_wave_slots", 4096, 1 << 31, [4095, (1 << 31) + 1], "max_wave_slots out of range"),
+    ("tail_wave_div", 0, 64, [65], "tail_wave_div must be in [0, 64]"),
+    ("lanes", 1, 8, [0, 9], "lanes must be in [1, 8]"),
+    ("lane_gate", 0, 1, [2], "lane_gate must be 0 or 1"),
+    ("l1_split", 0, 1, [2], "l1_split must be 0 or 1"),
+    ("plan_cache", 0, 1, [2], "plan_cache must be 0 or 1"),
+    ("xcd_order", 0, 1, [2], "xcd_order must be 0 or 1"),
+    ("group_docs", 0, 1, [2], "group_docs must be 0 or 1"),
+    ("runs_slots", 16, 64, [15, 48, 65], "runs_slots must be 16, 32 or 64"),
+    ("stile_text", 0, 2, [3], "stile_text must be 0, 1 or 2"),
+    ("text_scatter", 0, 1, [2], "text_scatter must be 0 or 1"),
+    ("contraction", 0, 2, [3], "contraction must be 0, 1 or 2"),
+    ("l1_group", 0, 2, [3], "l1_group must be 0, 1 or 2"),
+    ("rs_digit_bits", 0, 10, [9, 11], "rs_digit_bits must be 0, 8 or 10"),
+    ("nsq_list", 0, 2, [3], "nsq_list must be 0, 1 or 2"),
+    ("static_jumps", 0, 1, [2], "static_jumps must be 0 or 1"),
+    ("dead_skip", 0, 1, [2], "dead_skip must be 0 or 1"),
+    ("doctree_k32", 0, 1, [2], "doctree_k32 must be 0 or 1"),
+    ("level1", 0, 1, [2], "level1 must be 0 (auto) or 1 (global)"),
+    ("fuse_text", 0, (1 << 64) - 1, [], None),
+    ("doctree_lds_max", 0, (1 << 64) - 1, [], None),
+    ("glds_late", 0, (1 << 64) - 1, [], None),
+    ("plan_shrink", 0, (1 << 64) - 1, [], None),
+]
+
+
+def test_set_param_accepts_and_refuses_as_documented():
+    c = crdt_hip.Context(0)
+    for name, lo, hi, refused, msg in _PARAM_DOC:
+        c.set_param(name, lo)
+        c.set_param(name, hi)
+        for v in refused:
+            with pytest.raises(crdt_hip.CrdtHipError) as e:
+                c.set_param(name, v)
+            assert e.value.code == -1 and str(e.value) == "EINVAL: " + msg, (name, v)
+    with pytest.raises(crdt_hip.CrdtHipError) as e:
+        c.set_param("no_such_knob", 1)
+    assert e.value.code == -1 and str(e.value) == "EINVAL: unknown parameter no_such_knob"
+    c.close()
+
+
 @pytest.mark.parametrize("knob", ["xcd_order", "stile_text"])
 def test_level0_knobs_off_match_golden(golden, knob):
     """The XCD-aware tile order and the per-document text staged from the tile segments only
