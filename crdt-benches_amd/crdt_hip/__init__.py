@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from functools import partial as _partial
 
 import numpy as np
 
@@ -26,50 +27,6 @@ ERRORS = {
 }
 STAGES = ["classify", "runs", "sortb", "count", "scan", "place", "link", "walk1", "rank",
           "walk2", "expand", "digest", "doctree", "text", "encode"]
-
-# Every symbol include/crdt_hip.h declares (checked by tests/test_abi.py).
-EXPORTS = [
-    "crdt_hip_oplog_visible_bytes", "crdt_hip_oplog_apply_patches_bytes",
-    "crdt_hip_oplog_replace_bytes", "crdt_hip_oplog_patches_since_bytes",
-    "crdt_hip_replica_apply_patches_bytes", "crdt_hip_replica_replace_bytes",
-    "crdt_hip_replica_patches_since_bytes",
-    "crdt_hip_abi_version", "crdt_hip_device_count", "crdt_hip_init", "crdt_hip_destroy",
-    "crdt_hip_last_error", "crdt_hip_set_param", "crdt_hip_oplog_new", "crdt_hip_oplog_set_fugue",
-    "crdt_hip_oplog_set_agent", "crdt_hip_oplog_clone", "crdt_hip_trace_resolve_fugue",
-    "crdt_hip_replica_merge_inc",
-    "crdt_hip_oplog_free", "crdt_hip_oplog_insert", "crdt_hip_oplog_remove",
-    "crdt_hip_oplog_replace", "crdt_hip_oplog_visible_len", "crdt_hip_oplog_get_view",
-    "crdt_hip_oplog_version", "crdt_hip_oplog_encode_from", "crdt_hip_oplog_apply_update",
-    "crdt_hip_trace_load", "crdt_hip_trace_free", "crdt_hip_trace_len", "crdt_hip_trace_txns",
-    "crdt_hip_trace_patch", "crdt_hip_trace_start_content", "crdt_hip_trace_end_content",
-    "crdt_hip_trace_chars_to_bytes", "crdt_hip_trace_resolve", "crdt_hip_trace_resolve_many",
-    "crdt_hip_trace_save",
-    "crdt_hip_oplog_save", "crdt_hip_oplog_load", "crdt_hip_logfile_open",
-    "crdt_hip_logfile_close", "crdt_hip_synth_agents",
-    "crdt_hip_synth_tree", "crdt_hip_synth_tree_visible", "crdt_hip_merge", "crdt_hip_merge_batch", "crdt_hip_merge_order",
-    "crdt_hip_batch_create", "crdt_hip_batch_synth_tree", "crdt_hip_batch_free", "crdt_hip_batch_info",
-    "crdt_hip_batch_merge", "crdt_hip_batch_raw", "crdt_hip_replica_new", "crdt_hip_replica_clone",
-    "crdt_hip_replica_free", "crdt_hip_replica_apply_updates", "crdt_hip_replica_info",
-    "crdt_hip_updates_upload", "crdt_hip_updates_free", "crdt_hip_replica_apply_resident",
-    "crdt_hip_replica_merge", "crdt_hip_comm_unique_id", "crdt_hip_comm_init",
-    "crdt_hip_allgather_u64", "crdt_hip_comm_destroy", "crdt_hip_xxh64",
-    "crdt_hip_tree_digest", "crdt_hip_merge_len", "crdt_hip_replica_merge_len",
-    "crdt_hip_replica_replay", "crdt_hip_oplog_join", "crdt_hip_replica_join",
-    "crdt_hip_join_stats",
-    "crdt_hip_oplog_state_vector", "crdt_hip_oplog_encode_diff", "crdt_hip_oplog_apply_diff",
-    "crdt_hip_replica_state_vector", "crdt_hip_replica_encode_diff",
-    "crdt_hip_replica_apply_diff", "crdt_hip_delta_stats",
-    "crdt_hip_oplog_mark", "crdt_hip_mark_free", "crdt_hip_oplog_patches_since",
-    "crdt_hip_replica_mark", "crdt_hip_replica_patches_since", "crdt_hip_patch_stats",
-    "crdt_hip_oplog_apply_patches", "crdt_hip_replica_set_agent",
-    "crdt_hip_replica_apply_patches", "crdt_hip_replica_replace", "crdt_hip_edit_stats",
-    "crdt_hip_oplog_anchors_at", "crdt_hip_oplog_anchors_at_bytes",
-    "crdt_hip_oplog_anchors_resolve", "crdt_hip_replica_anchors_at",
-    "crdt_hip_replica_anchors_at_bytes", "crdt_hip_replica_anchors_resolve",
-    "crdt_hip_anchor_stats",
-    "crdt_hip_oplog_spans", "crdt_hip_replica_spans", "crdt_hip_format_stats",
-    "crdt_hip_oplog_text_at", "crdt_hip_replica_text_at", "crdt_hip_text_stats",
-]
 
 
 class CrdtHipError(RuntimeError):
@@ -113,21 +70,12 @@ class Stats(C.Structure):
         }
 
 
-_LIB = None
-
-
-def lib() -> C.CDLL:
-    """Load libcrdt_hip.so from the package directory (fails loudly if it is not built)."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"{LIB_PATH} is not built: run `make -C {PKG_DIR}` "
-                           "(or __graft_entry__.build())")
-    L = C.CDLL(LIB_PATH)
+# (restype, argtypes) of every symbol include/crdt_hip.h declares; lib() sets them, and EXPORTS is
+# their names (tests/test_abi.py compares it with the header: a declared symbol has argtypes).
+def _signatures() -> dict:
     vp, u32, u64, sz, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_size_t, C.c_int
     P = C.POINTER
-    sig = {
+    return {
         "crdt_hip_abi_version": (i32, []),
         "crdt_hip_device_count": (i32, [P(i32)]),
         "crdt_hip_init": (i32, [i32, P(vp)]),
@@ -236,7 +184,23 @@ def lib() -> C.CDLL:
         "crdt_hip_xxh64": (u64, [vp, sz, u64]),
         "crdt_hip_tree_digest": (u64, [vp, sz]),
     }
-    for name, (res, args) in sig.items():
+
+
+_SIG = _signatures()
+EXPORTS = list(_SIG)
+_LIB = None
+
+
+def lib() -> C.CDLL:
+    """Load libcrdt_hip.so from the package directory (fails loudly if it is not built)."""
+    global _LIB
+    if _LIB is not None:
+        return _LIB
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(f"{LIB_PATH} is not built: run `make -C {PKG_DIR}` "
+                           "(or __graft_entry__.build())")
+    L = C.CDLL(LIB_PATH)
+    for name, (res, args) in _SIG.items():
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args
@@ -589,8 +553,193 @@ def _span_list(raw: tuple) -> tuple:
             for x in sp], pend
 
 
-class OpLog:
+def _outs(call, n: int, ctx=None, ctype=C.c_uint64) -> tuple:
+    """call(p0, ..., p[n-1]) with n out-pointers of `ctype` -> the n values."""
+    v = [ctype() for _ in range(n)]
+    _check(call(*map(C.byref, v)), ctx)
+    return tuple([x.value for x in v])
+
+
+def _pair(call, ctx=None) -> tuple:
+    """call(added, tombstoned) -> (items appended, items tombstoned), the out-pair of every call
+    that changes a log or a replica."""
+    return _outs(call, 2, ctx, C.c_uint32)
+
+
+class _Document:
+    """What an OpLog and a Replica both are: a document that is synced by deltas, marked, read as
+    patches, text windows, anchors and spans, and edited by patches (crdt_hip_oplog_* and
+    crdt_hip_replica_* take the same arguments after their handles).  Every docstring says what the
+    call does on the log, which is the definition; the replica returns the same thing, byte for
+    byte, from HIP kernels over its kept document order, and a call leaves it as a merge_inc would.
+    A subclass gives the symbol prefix, the leading handle arguments, the error context and the
+    first capacities to try."""
+
+    _PREFIX = ""                # "crdt_hip_oplog_" or "crdt_hip_replica_"
+    _GUESS_SV = 0               # state_vector: entries
+    _GUESS_DIFF = 0             # encode_diff: bytes
+    _GUESS_PATCHES = (0, 0)     # patches_since: patches, inserted bytes
+    _GUESS_TEXT = 1 << 12       # text_at: bytes
+    _fns: dict                  # this class's C functions by short name, resolved at first use
+
+    def _lead(self) -> tuple:   # the handles every call starts with
+        raise NotImplementedError
+
+    _ectx = None                # whose error string a failed call wrote: a context handle, or None
+
+    def _bind(self, name: str):
+        """crdt_hip_<kind>_<name> with this document's handles in front."""
+        f = self._fns.get(name)
+        if f is None:
+            f = self._fns[name] = getattr(lib(), self._PREFIX + name)
+        return _partial(f, *self._lead())
+
+    # State-vector delta sync (crdt_hip.h, "state-vector delta sync").
+    def state_vector(self) -> list:
+        """Per agent with an item, the largest lamport among its items: [(agent, lamport)] by agent
+        ascending."""
+        return _sv_get(self._bind("state_vector"), self._ectx, self._GUESS_SV)
+
+    def encode_diff(self, sv) -> bytes:
+        """The delta a peer with state vector `sv` lacks: the items `sv` does not cover, and the
+        tombstones of the items it covers as identity ranges.  The document is unchanged."""
+        arr, nsv = _sv_pack(sv)
+        call = self._bind("encode_diff")
+        return _diff_get(lambda *a: call(arr, nsv, *a), self._ectx, self._GUESS_DIFF)
+
+    def apply_diff(self, data: bytes) -> tuple:
+        """this document <- this document U delta.  Returns (items appended, items it held that
+        became deleted); a rejected delta raises and changes nothing."""
+        call = self._bind("apply_diff")
+        return _pair(lambda *a: call(data, len(data), *a), self._ectx)
+
+    # Patches since a mark, and text windows (crdt_hip.h, "patches since a mark", "text windows").
+    def mark(self) -> Mark:
+        """Remember this version of the document (a replica: its tombstone bits packed into a
+        device bit plane the mark owns)."""
+        h = C.c_void_p()
+        _check(self._bind("mark")(C.byref(h)), self._ectx)
+        return Mark(h, self)
+
+    def _patches_since(self, name: str, mark: Mark) -> tuple:
+        call = self._bind(name)
+        return _patches_get(lambda *a: call(mark._h, *a), self._ectx, self._GUESS_PATCHES)
+
+    def patches_since_raw(self, mark: Mark) -> tuple:
+        """patches_since as (crdt_hip_patch array as a structured numpy array, `ins` bytes)."""
+        return self._patches_since("patches_since", mark)
+
+    def patches_since(self, mark: Mark) -> list:
+        """What changed in the document since `mark`, as [(pos, del, ins: str)] ascending in pos:
+        applied in that order, each as replace(pos, pos + del, ins), to the text at the mark they
+        give the text now."""
+        return _patch_list(self.patches_since_raw(mark))
+
+    def patches_since_bytes_raw(self, mark: Mark) -> tuple:
+        """patches_since_bytes as (crdt_hip_patch array, `ins` bytes)."""
+        return self._patches_since("patches_since_bytes", mark)
+
+    def patches_since_bytes(self, mark: Mark) -> list:
+        """patches_since with pos and del in UTF-8 bytes: spliced in order into the UTF-8 of the
+        text at the mark they give the UTF-8 now."""
+        return _patch_list(self.patches_since_bytes_raw(mark))
+
+    def text_at(self, mark: Mark = None, start: int = 0, end: int = None, bytes: bool = False) -> bytes:
+        """The UTF-8 of window [start, end) of the version now (`mark` None) or at `mark`, in
+        codepoints or, with `bytes`, in UTF-8 bytes; `end` None is the version's end.  The text at
+        a mark is byte for byte what the document held when the mark was taken.  (A replica writes
+        only the tiles of its document order that the window overlaps.)"""
+        return _text_get(self._bind("text_at"), mark, start, end, bytes, self._ectx,
+                         guess=self._GUESS_TEXT)[0]
+
+    def text_info(self, mark: Mark = None, start: int = 0, end: int = None, bytes: bool = False) -> dict:
+        """crdt_hip_text_info of that window alone: len, len_bytes, start, start_bytes, n, n_bytes
+        (a position translation between codepoints and bytes; a replica: the count and scan, no
+        write pass)."""
+        return _text_get(self._bind("text_at"), mark, start, end, bytes, self._ectx, info_only=True)
+
+    # Local edits, in codepoints and in UTF-8 bytes (crdt_hip.h, "local edits", "byte offsets").  A
+    # byte call on a log walks the whole document; a replica translates the boundaries to codepoint
+    # ranks in HIP kernels against its kept order, and keeps no text on the host.
+    def _apply_patches(self, name: str, patches, ins) -> tuple:
+        arr, text = _patches_pack(patches, ins)
+        call = self._bind(name)
+        return _pair(lambda *a: call(arr.ctypes.data if arr.size else None, arr.size, text, len(text),
+                                     *a), self._ectx)
+
+    def apply_patches(self, patches, ins=None) -> tuple:
+        """Local edits as a set of positional patches in the patches_since convention:
+        [(pos, del, ins: str)] ascending and non-touching, each applied as
+        replace(pos, pos + del, ins) to the document as the earlier ones left it (a replica: the
+        same resulting log, slot for slot).  Returns (items appended, items deleted); a rejected
+        call raises and changes nothing."""
+        return self._apply_patches("apply_patches", patches, ins)
+
+    def apply_patches_bytes(self, patches, ins=None) -> tuple:
+        """apply_patches with pos and del in UTF-8 bytes: the log apply_patches gives for the
+        patches translated through the text before the call.  A boundary inside a codepoint raises
+        EINVAL.  Returns (items appended, items deleted)."""
+        return self._apply_patches("apply_patches_bytes", patches, ins)
+
+    def replace_bytes(self, start: int, end: int, text: str) -> None:
+        """Upstream::replace in byte offsets: one patch."""
+        b = text.encode("utf-8")
+        _check(self._bind("replace_bytes")(start, end, b, len(b)), self._ectx)
+
+    def insert_bytes(self, pos: int, text: str) -> None:
+        self.replace_bytes(pos, pos, text)
+
+    def remove_bytes(self, start: int, end: int) -> None:
+        if end < start:
+            raise CrdtHipError(-2, "remove range out of range")
+        self.replace_bytes(start, end, "")
+
+    # Anchors and formats (crdt_hip.h, "anchors", "formats").  A call on a log walks the whole
+    # document; a call on a replica changes no log contents.
+    def anchors_at_raw(self, positions, bias=AFTER, out=None) -> np.ndarray:
+        return _anchors_at(self._bind("anchors_at"), positions, bias, self._ectx, out)
+
+    def anchors_at_bytes_raw(self, positions, bias=AFTER, out=None) -> np.ndarray:
+        return _anchors_at(self._bind("anchors_at_bytes"), positions, bias, self._ectx, out)
+
+    def resolve_anchors_raw(self, anchors, out=None) -> np.ndarray:
+        return _anchors_resolve(self._bind("anchors_resolve"), anchors, self._ectx, out)
+
+    def anchors_at(self, positions, bias=AFTER) -> list:
+        """Gap positions 0..len of the visible document (codepoints) -> [(id, bias)]: AFTER names
+        the item before the gap, BEFORE the one after it, EDGE the document's start or end.
+        `bias`: a scalar or one per position."""
+        return _anchor_list(self.anchors_at_raw(positions, bias))
+
+    def anchors_at_bytes(self, positions, bias=AFTER) -> list:
+        """anchors_at with positions in UTF-8 bytes; one inside a codepoint raises EINVAL."""
+        return _anchor_list(self.anchors_at_bytes_raw(positions, bias))
+
+    def resolve_anchors(self, anchors) -> list:
+        """[(id, bias)], made here or on any peer -> [(pos, pos_bytes, state)] in the visible
+        document now; state LIVE, DEAD (the item is tombstoned: the anchor lies where it was) or
+        UNKNOWN (the document does not hold the item yet)."""
+        return _anchor_pos_list(self.resolve_anchors_raw(anchors))
+
+    def spans_raw(self, formats, out=None) -> tuple:
+        return _spans_get(self._bind("spans"), formats, self._ectx, out)
+
+    def spans(self, formats) -> tuple:
+        """Attribute ranges [(start, end, key, value, op, flags)] (start, end: anchors (id, bias);
+        flags 0 or REMOVE) -> ([(pos, len, pos_bytes, len_bytes, {key: value})], pending): the
+        non-overlapping spans of the visible document, per key the covering format with the largest
+        op winning, and the formats whose anchors this document cannot place yet."""
+        return _span_list(self.spans_raw(formats))
+
+
+class OpLog(_Document):
     """Host-side resolver (positional patches -> anchor op log), crdt_hip_oplog_*."""
+
+    _PREFIX = "crdt_hip_oplog_"
+    _fns: dict = {}
+
+    def _lead(self) -> tuple:
+        return (self._h,)
 
     def __init__(self, handle=None, fugue: bool = False, agent: int = 0):
         if handle is None:
@@ -626,10 +775,7 @@ class OpLog:
         part of its identity.  The kind is the presence of the side column (OpLog(fugue=True),
         LogArrays with `side`), never its contents; a mixed pair raises EINVAL."""
         v, keep = _as_view(other)
-        a, t = C.c_uint32(), C.c_uint32()
-        _check(lib().crdt_hip_oplog_join(self._h, C.byref(v), C.byref(a), C.byref(t)))
-        del keep
-        return int(a.value), int(t.value)
+        return _pair(lambda *a: lib().crdt_hip_oplog_join(self._h, C.byref(v), *a))
 
     def insert(self, pos: int, text: str) -> None:
         b = text.encode("utf-8")
@@ -669,161 +815,14 @@ class OpLog:
         return int(lib().crdt_hip_oplog_version(self._h))
 
     def encode_from(self, version: int) -> bytes:
-        need = C.c_size_t(0)
-        rc = lib().crdt_hip_oplog_encode_from(self._h, version, None, 0, C.byref(need))
-        if rc not in (OK, -6):
-            _check(rc)
-        buf = C.create_string_buffer(max(need.value, 1))
-        _check(lib().crdt_hip_oplog_encode_from(self._h, version, buf, need.value,
-                                                C.byref(need)))
-        return buf.raw[: need.value]
+        return _diff_get(lambda *a: lib().crdt_hip_oplog_encode_from(self._h, version, *a))
 
     def apply_update(self, update: bytes) -> None:
         _check(lib().crdt_hip_oplog_apply_update(self._h, update, len(update)))
 
-    def state_vector(self) -> list:
-        """Per agent with an item, the largest lamport among its items: [(agent, lamport)] by agent
-        ascending (crdt_hip_oplog_state_vector)."""
-        return _sv_get(lambda out, cap, n: lib().crdt_hip_oplog_state_vector(self._h, out, cap, n))
-
-    def encode_diff(self, sv) -> bytes:
-        """The delta a peer with state vector `sv` lacks (crdt_hip_oplog_encode_diff): the items
-        `sv` does not cover, and the tombstones of the items it covers as identity ranges."""
-        arr, nsv = _sv_pack(sv)
-        return _diff_get(lambda buf, cap, n: lib().crdt_hip_oplog_encode_diff(
-            self._h, arr, nsv, buf, cap, n))
-
-    def apply_diff(self, data: bytes) -> tuple:
-        """this log <- this log U delta (crdt_hip_oplog_apply_diff).  Returns (items appended, items
-        this log held that became deleted); a rejected delta raises and changes nothing."""
-        a, t = C.c_uint32(), C.c_uint32()
-        _check(lib().crdt_hip_oplog_apply_diff(self._h, data, len(data), C.byref(a), C.byref(t)))
-        return int(a.value), int(t.value)
-
-    def mark(self) -> Mark:
-        """Remember this version of the log (crdt_hip_oplog_mark)."""
-        h = C.c_void_p()
-        _check(lib().crdt_hip_oplog_mark(self._h, C.byref(h)))
-        return Mark(h, self)
-
-    def patches_since_raw(self, mark: Mark) -> tuple:
-        """(crdt_hip_patch array as a structured numpy array, `ins` bytes) of
-        crdt_hip_oplog_patches_since."""
-        return _patches_get(lambda *a: lib().crdt_hip_oplog_patches_since(self._h, mark._h, *a))
-
-    def patches_since(self, mark: Mark) -> list:
-        """What changed in the document since `mark`, as [(pos, del, ins: str)] ascending in pos:
-        applied in that order, each as replace(pos, pos + del, ins), to the text at the mark they
-        give the text now (crdt_hip_oplog_patches_since)."""
-        return _patch_list(self.patches_since_raw(mark))
-
-    def text_at(self, mark: Mark = None, start: int = 0, end: int = None, bytes: bool = False) -> bytes:
-        """The UTF-8 of window [start, end) of the version now (`mark` None) or at `mark`, in
-        codepoints or, with `bytes`, in UTF-8 bytes; `end` None is the version's end
-        (crdt_hip_oplog_text_at).  The text at a mark is byte for byte what the log held when the
-        mark was taken."""
-        return _text_get(lambda *a: lib().crdt_hip_oplog_text_at(self._h, *a), mark, start, end,
-                         bytes, guess=1 << 12)[0]
-
-    def text_info(self, mark: Mark = None, start: int = 0, end: int = None, bytes: bool = False) -> dict:
-        """crdt_hip_text_info of that window alone: len, len_bytes, start, start_bytes, n, n_bytes
-        (a position translation between codepoints and bytes)."""
-        return _text_get(lambda *a: lib().crdt_hip_oplog_text_at(self._h, *a), mark, start, end,
-                         bytes, info_only=True)
-
-    def apply_patches(self, patches, ins=None) -> tuple:
-        """Local edits as a set of positional patches in the patches_since convention
-        (crdt_hip_oplog_apply_patches): [(pos, del, ins: str)] ascending and non-touching, each
-        applied as replace(pos, pos + del, ins) to the document as the earlier ones left it.
-        Returns (items appended, items deleted); a rejected call raises and changes nothing."""
-        arr, text = _patches_pack(patches, ins)
-        a, t = C.c_uint32(), C.c_uint32()
-        _check(lib().crdt_hip_oplog_apply_patches(
-            self._h, arr.ctypes.data if arr.size else None, arr.size, text, len(text),
-            C.byref(a), C.byref(t)))
-        return int(a.value), int(t.value)
-
-    # Byte offsets (crdt_hip.h, "byte offsets"): the same calls with pos and del in UTF-8 bytes of
-    # the visible document.  The host calls are the definition the device calls are held to; a call
-    # walks the whole document.
     def visible_bytes(self) -> int:
         """UTF-8 bytes of the visible document (crdt_hip_oplog_visible_bytes)."""
-        b = C.c_uint64()
-        _check(lib().crdt_hip_oplog_visible_bytes(self._h, C.byref(b)))
-        return int(b.value)
-
-    def apply_patches_bytes(self, patches, ins=None) -> tuple:
-        """apply_patches with pos and del in UTF-8 bytes (crdt_hip_oplog_apply_patches_bytes): the
-        log apply_patches gives for the patches translated through the text before the call.  A
-        boundary inside a codepoint raises EINVAL.  Returns (items appended, items deleted)."""
-        arr, text = _patches_pack(patches, ins)
-        a, t = C.c_uint32(), C.c_uint32()
-        _check(lib().crdt_hip_oplog_apply_patches_bytes(
-            self._h, arr.ctypes.data if arr.size else None, arr.size, text, len(text),
-            C.byref(a), C.byref(t)))
-        return int(a.value), int(t.value)
-
-    def replace_bytes(self, start: int, end: int, text: str) -> None:
-        b = text.encode("utf-8")
-        _check(lib().crdt_hip_oplog_replace_bytes(self._h, start, end, b, len(b)))
-
-    def insert_bytes(self, pos: int, text: str) -> None:
-        self.replace_bytes(pos, pos, text)
-
-    def remove_bytes(self, start: int, end: int) -> None:
-        if end < start:
-            raise CrdtHipError(-2, "remove range out of range")
-        self.replace_bytes(start, end, "")
-
-    def patches_since_bytes_raw(self, mark: Mark) -> tuple:
-        return _patches_get(lambda *a: lib().crdt_hip_oplog_patches_since_bytes(
-            self._h, mark._h, *a))
-
-    def patches_since_bytes(self, mark: Mark) -> list:
-        """patches_since with pos and del in UTF-8 bytes: spliced in order into the UTF-8 of the
-        text at the mark they give the UTF-8 now (crdt_hip_oplog_patches_since_bytes)."""
-        return _patch_list(self.patches_since_bytes_raw(mark))
-
-    # Anchors (crdt_hip.h, "anchors").  The host calls are the definition the device calls are held
-    # to; a call walks the whole document.
-    def anchors_at_raw(self, positions, bias=AFTER, out=None) -> np.ndarray:
-        return _anchors_at(lambda *a: lib().crdt_hip_oplog_anchors_at(self._h, *a), positions, bias,
-                           out=out)
-
-    def anchors_at_bytes_raw(self, positions, bias=AFTER, out=None) -> np.ndarray:
-        return _anchors_at(lambda *a: lib().crdt_hip_oplog_anchors_at_bytes(self._h, *a), positions,
-                           bias, out=out)
-
-    def resolve_anchors_raw(self, anchors, out=None) -> np.ndarray:
-        return _anchors_resolve(lambda *a: lib().crdt_hip_oplog_anchors_resolve(self._h, *a),
-                                anchors, out=out)
-
-    def anchors_at(self, positions, bias=AFTER) -> list:
-        """Gap positions 0..len of the visible document (codepoints) -> [(id, bias)]: AFTER names
-        the item before the gap, BEFORE the one after it, EDGE the document's start or end
-        (crdt_hip_oplog_anchors_at).  `bias`: a scalar or one per position."""
-        return _anchor_list(self.anchors_at_raw(positions, bias))
-
-    def anchors_at_bytes(self, positions, bias=AFTER) -> list:
-        """anchors_at with positions in UTF-8 bytes; one inside a codepoint raises EINVAL."""
-        return _anchor_list(self.anchors_at_bytes_raw(positions, bias))
-
-    def resolve_anchors(self, anchors) -> list:
-        """[(id, bias)], made here or on any peer -> [(pos, pos_bytes, state)] in the visible
-        document now; state LIVE, DEAD (the item is tombstoned: the anchor lies where it was) or
-        UNKNOWN (the log does not hold the item yet) (crdt_hip_oplog_anchors_resolve)."""
-        return _anchor_pos_list(self.resolve_anchors_raw(anchors))
-
-    # Formats (crdt_hip.h, "formats").  The host call is the definition the device call is held to.
-    def spans_raw(self, formats, out=None) -> tuple:
-        return _spans_get(lambda *a: lib().crdt_hip_oplog_spans(self._h, *a), formats, out=out)
-
-    def spans(self, formats) -> tuple:
-        """Attribute ranges [(start, end, key, value, op, flags)] (start, end: anchors (id, bias);
-        flags 0 or REMOVE) -> ([(pos, len, pos_bytes, len_bytes, {key: value})], pending): the
-        non-overlapping spans of the visible document, per key the covering format with the largest
-        op winning, and the formats whose anchors this log cannot place yet (crdt_hip_oplog_spans)."""
-        return _span_list(self.spans_raw(formats))
+        return _outs(lambda *a: lib().crdt_hip_oplog_visible_bytes(self._h, *a), 1)[0]
 
     def save(self, path: str) -> None:
         """Op-log file (crdt_hip_oplog_save): 64-byte-aligned SoA arrays."""
@@ -978,63 +977,41 @@ class Context:
     def set_param(self, key: str, value: int) -> None:
         _check(lib().crdt_hip_set_param(self._h, key.encode(), value), self._h)
 
+    def _stats(self, name: str, fields: tuple) -> dict:
+        """crdt_hip_<name>_stats: what this context's last device call of that kind observed."""
+        fn = getattr(lib(), f"crdt_hip_{name}_stats")
+        return dict(zip(fields, _outs(lambda *a: fn(self._h, *a), len(fields), self._h)))
+
     def join_stats(self) -> dict:
         """What this context's last Replica.join observed (crdt_hip_join_stats)."""
-        p, t, c, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().crdt_hip_join_stats(self._h, C.byref(p), C.byref(t), C.byref(c),
-                                         C.byref(ns)), self._h)
-        return {"prefix_slots": int(p.value), "table_slots": int(t.value),
-                "table_capacity": int(c.value), "device_ns": int(ns.value)}
+        return self._stats("join", ("prefix_slots", "table_slots", "table_capacity", "device_ns"))
 
     def delta_stats(self) -> dict:
         """What this context's last Replica.encode_diff or apply_diff observed
         (crdt_hip_delta_stats)."""
-        i, r, t, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().crdt_hip_delta_stats(self._h, C.byref(i), C.byref(r), C.byref(t),
-                                          C.byref(ns)), self._h)
-        return {"items": int(i.value), "ranges": int(r.value), "table_slots": int(t.value),
-                "device_ns": int(ns.value)}
+        return self._stats("delta", ("items", "ranges", "table_slots", "device_ns"))
 
     def patch_stats(self) -> dict:
         """What this context's last Replica.patches_since observed (crdt_hip_patch_stats)."""
-        p, b, r, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().crdt_hip_patch_stats(self._h, C.byref(p), C.byref(b), C.byref(r),
-                                          C.byref(ns)), self._h)
-        return {"patches": int(p.value), "ins_bytes": int(b.value), "ranks": int(r.value),
-                "device_ns": int(ns.value)}
+        return self._stats("patch", ("patches", "ins_bytes", "ranks", "device_ns"))
 
     def edit_stats(self) -> dict:
         """What this context's last Replica.apply_patches (or replace, insert, remove) observed
         (crdt_hip_edit_stats)."""
-        p, i, t, r, ns = (C.c_uint64() for _ in range(5))
-        _check(lib().crdt_hip_edit_stats(self._h, C.byref(p), C.byref(i), C.byref(t), C.byref(r),
-                                         C.byref(ns)), self._h)
-        return {"patches": int(p.value), "items": int(i.value), "tombstones": int(t.value),
-                "ranks": int(r.value), "device_ns": int(ns.value)}
+        return self._stats("edit", ("patches", "items", "tombstones", "ranks", "device_ns"))
 
     def anchor_stats(self) -> dict:
         """What this context's last Replica.anchors_at or resolve_anchors observed
         (crdt_hip_anchor_stats)."""
-        a, u, r, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().crdt_hip_anchor_stats(self._h, C.byref(a), C.byref(u), C.byref(r),
-                                           C.byref(ns)), self._h)
-        return {"anchors": int(a.value), "unknown": int(u.value), "ranks": int(r.value),
-                "device_ns": int(ns.value)}
+        return self._stats("anchor", ("anchors", "unknown", "ranks", "device_ns"))
 
     def text_stats(self) -> dict:
         """What this context's last Replica.text_at or text_info observed (crdt_hip_text_stats)."""
-        r, t, b, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().crdt_hip_text_stats(self._h, C.byref(r), C.byref(t), C.byref(b), C.byref(ns)),
-               self._h)
-        return {"ranks": int(r.value), "tiles_written": int(t.value), "bytes": int(b.value),
-                "device_ns": int(ns.value)}
+        return self._stats("text", ("ranks", "tiles_written", "bytes", "device_ns"))
 
     def format_stats(self) -> dict:
         """What this context's last Replica.spans observed (crdt_hip_format_stats)."""
-        v = [C.c_uint64() for _ in range(6)]
-        _check(lib().crdt_hip_format_stats(self._h, *[C.byref(x) for x in v]), self._h)
-        names = ("formats", "pending", "segments", "spans", "ranks", "device_ns")
-        return {k: int(x.value) for k, x in zip(names, v)}
+        return self._stats("format", ("formats", "pending", "segments", "spans", "ranks", "device_ns"))
 
     def merge(self, log) -> tuple:
         """Merged document: (utf8 bytes, tree digest)."""
@@ -1058,10 +1035,7 @@ class Context:
         """Upstream::len on the device: (codepoints, UTF-8 bytes, tree digest) of the merged
         document, without copying the text back (crdt_hip_merge_len)."""
         v, keep = _as_view(log)
-        c, n, d = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().crdt_hip_merge_len(self._h, C.byref(v), C.byref(c), C.byref(n), C.byref(d)),
-               self._h)
-        return int(c.value), int(n.value), int(d.value)
+        return _outs(lambda *a: lib().crdt_hip_merge_len(self._h, C.byref(v), *a), 3, self._h)
 
     def merge_batch(self, logs: list, stats: bool = False):
         views = []
@@ -1136,9 +1110,8 @@ class Batch:
                                                C.byref(h)), ctx._h)
         self._h = h
         self.ctx = ctx
-        docs, items, dev = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().crdt_hip_batch_info(h, C.byref(docs), C.byref(items), C.byref(dev)))
-        self.docs, self.items, self.device_bytes = int(docs.value), int(items.value), int(dev.value)
+        self.docs, self.items, self.device_bytes = _outs(
+            lambda *a: lib().crdt_hip_batch_info(h, *a), 3)
 
     @classmethod
     def synth_tree(cls, ctx: Context, n_items: int, p_chain_pct: int, del_pct: int,
@@ -1202,12 +1175,24 @@ class UpdateBatch:
     __del__ = close
 
 
-class Replica:
+class Replica(_Document):
     """Device-resident replica (crdt_hip_replica_*): Downstream on the device.
 
     Updates (OpLog.encode_from's wire format) are decoded by the HIP kernels straight into the
     replica's HBM slot arrays, a whole batch per call, and the replica is merged where it lies.
     """
+
+    _PREFIX = "crdt_hip_replica_"
+    _fns: dict = {}
+    # (a device call scans or streams the whole replica every time: room for most answers at once)
+    _GUESS_SV, _GUESS_DIFF, _GUESS_PATCHES, _GUESS_TEXT = 256, 1 << 20, (4096, 1 << 16), 1 << 16
+
+    def _lead(self) -> tuple:
+        return (self.ctx._h, self._h)
+
+    @property
+    def _ectx(self):
+        return self.ctx._h
 
     def __init__(self, ctx: Context, init=None, _handle=None):
         if _handle is None:
@@ -1258,77 +1243,13 @@ class Replica:
         nothing.  Two RGA replicas or two Fugue replicas (made from a Fugue log or view, empty or
         not): a Fugue item's identity is its key without the side bit, and an appended item keeps
         its side; a mixed pair raises EINVAL."""
-        a, t = C.c_uint32(), C.c_uint32()
-        _check(lib().crdt_hip_replica_join(self.ctx._h, self._h, other._h, C.byref(a),
-                                           C.byref(t)), self.ctx._h)
-        return int(a.value), int(t.value)
-
-    def state_vector(self) -> list:
-        """OpLog.state_vector on the device (crdt_hip_replica_state_vector)."""
-        return _sv_get(lambda out, cap, n: lib().crdt_hip_replica_state_vector(
-            self.ctx._h, self._h, out, cap, n), self.ctx._h, guess=256)
-
-    def encode_diff(self, sv) -> bytes:
-        """OpLog.encode_diff on the device (crdt_hip_replica_encode_diff): the same bytes; this
-        replica is unchanged."""
-        arr, nsv = _sv_pack(sv)
-        return _diff_get(lambda buf, cap, n: lib().crdt_hip_replica_encode_diff(
-            self.ctx._h, self._h, arr, nsv, buf, cap, n), self.ctx._h, guess=1 << 20)
-
-    def apply_diff(self, data: bytes) -> tuple:
-        """OpLog.apply_diff on the device (crdt_hip_replica_apply_diff): the same resulting log,
-        slot for slot; a rejected delta raises and changes nothing."""
-        a, t = C.c_uint32(), C.c_uint32()
-        _check(lib().crdt_hip_replica_apply_diff(self.ctx._h, self._h, data, len(data),
-                                                 C.byref(a), C.byref(t)), self.ctx._h)
-        return int(a.value), int(t.value)
-
-    def mark(self) -> Mark:
-        """Remember this version of the replica (crdt_hip_replica_mark): its tombstone bits packed
-        into a device bit plane the mark owns."""
-        h = C.c_void_p()
-        _check(lib().crdt_hip_replica_mark(self.ctx._h, self._h, C.byref(h)), self.ctx._h)
-        return Mark(h, self)
-
-    def patches_since_raw(self, mark: Mark) -> tuple:
-        """(crdt_hip_patch array as a structured numpy array, `ins` bytes) of
-        crdt_hip_replica_patches_since."""
-        return _patches_get(lambda *a: lib().crdt_hip_replica_patches_since(
-            self.ctx._h, self._h, mark._h, *a), self.ctx._h, guess=(4096, 1 << 16))
-
-    def patches_since(self, mark: Mark) -> list:
-        """OpLog.patches_since on the device (crdt_hip_replica_patches_since): the same patches.
-        Leaves the replica as a merge_inc would."""
-        return _patch_list(self.patches_since_raw(mark))
-
-    def text_at(self, mark: Mark = None, start: int = 0, end: int = None, bytes: bool = False) -> bytes:
-        """OpLog.text_at on the device (crdt_hip_replica_text_at): the same bytes, from kernels that
-        write only the tiles of the document order the window overlaps.  Leaves the replica as a
-        merge_inc would."""
-        return _text_get(lambda *a: lib().crdt_hip_replica_text_at(self.ctx._h, self._h, *a), mark,
-                         start, end, bytes, self.ctx._h, guess=1 << 16)[0]
-
-    def text_info(self, mark: Mark = None, start: int = 0, end: int = None, bytes: bool = False) -> dict:
-        """OpLog.text_info on the device: the count and scan alone, no write pass."""
-        return _text_get(lambda *a: lib().crdt_hip_replica_text_at(self.ctx._h, self._h, *a), mark,
-                         start, end, bytes, self.ctx._h, info_only=True)
+        return _pair(lambda *a: lib().crdt_hip_replica_join(self.ctx._h, self._h, other._h, *a),
+                     self.ctx._h)
 
     def set_agent(self, agent: int) -> None:
         """The agent id of this replica's later local edits (crdt_hip_replica_set_agent; default
         0, kept by a clone)."""
         _check(lib().crdt_hip_replica_set_agent(self._h, agent))
-
-    def apply_patches(self, patches, ins=None) -> tuple:
-        """OpLog.apply_patches on the device (crdt_hip_replica_apply_patches): the same resulting
-        log, slot for slot, with the positions resolved in HIP kernels against the replica's kept
-        document order.  Returns (items appended, items deleted); a rejected call raises and
-        changes nothing."""
-        arr, text = _patches_pack(patches, ins)
-        a, t = C.c_uint32(), C.c_uint32()
-        _check(lib().crdt_hip_replica_apply_patches(
-            self.ctx._h, self._h, arr.ctypes.data if arr.size else None, arr.size, text, len(text),
-            C.byref(a), C.byref(t)), self.ctx._h)
-        return int(a.value), int(t.value)
 
     def replace(self, start: int, end: int, text: str) -> None:
         """Upstream::replace on the device (crdt_hip_replica_replace): one patch."""
@@ -1344,85 +1265,9 @@ class Replica:
             raise CrdtHipError(-2, "remove range out of range")
         self.replace(start, end, "")
 
-    # Byte offsets (crdt_hip.h, "byte offsets"): the boundaries are translated to codepoint ranks
-    # in HIP kernels against the kept order; no text is kept on the host.
-    def apply_patches_bytes(self, patches, ins=None) -> tuple:
-        """OpLog.apply_patches_bytes on the device (crdt_hip_replica_apply_patches_bytes): the same
-        resulting log, slot for slot.  Returns (items appended, items deleted); a rejected call
-        raises and changes nothing."""
-        arr, text = _patches_pack(patches, ins)
-        a, t = C.c_uint32(), C.c_uint32()
-        _check(lib().crdt_hip_replica_apply_patches_bytes(
-            self.ctx._h, self._h, arr.ctypes.data if arr.size else None, arr.size, text, len(text),
-            C.byref(a), C.byref(t)), self.ctx._h)
-        return int(a.value), int(t.value)
-
-    def replace_bytes(self, start: int, end: int, text: str) -> None:
-        """Upstream::replace in byte offsets on the device (crdt_hip_replica_replace_bytes)."""
-        b = text.encode("utf-8")
-        _check(lib().crdt_hip_replica_replace_bytes(self.ctx._h, self._h, start, end, b, len(b)),
-               self.ctx._h)
-
-    def insert_bytes(self, pos: int, text: str) -> None:
-        self.replace_bytes(pos, pos, text)
-
-    def remove_bytes(self, start: int, end: int) -> None:
-        if end < start:
-            raise CrdtHipError(-2, "remove range out of range")
-        self.replace_bytes(start, end, "")
-
-    def patches_since_bytes_raw(self, mark: Mark) -> tuple:
-        """(crdt_hip_patch array as a structured numpy array, `ins` bytes) of
-        crdt_hip_replica_patches_since_bytes."""
-        return _patches_get(lambda *a: lib().crdt_hip_replica_patches_since_bytes(
-            self.ctx._h, self._h, mark._h, *a), self.ctx._h, guess=(4096, 1 << 16))
-
-    def patches_since_bytes(self, mark: Mark) -> list:
-        """OpLog.patches_since_bytes on the device: the same patches."""
-        return _patch_list(self.patches_since_bytes_raw(mark))
-
-    # Anchors (crdt_hip.h, "anchors"): the same arrays as the OpLog calls, byte for byte, from HIP
-    # kernels over the kept document order and its inverse.  A call leaves the replica as a
-    # merge_inc would and changes no log contents.
-    def anchors_at_raw(self, positions, bias=AFTER, out=None) -> np.ndarray:
-        return _anchors_at(lambda *a: lib().crdt_hip_replica_anchors_at(self.ctx._h, self._h, *a),
-                           positions, bias, self.ctx._h, out)
-
-    def anchors_at_bytes_raw(self, positions, bias=AFTER, out=None) -> np.ndarray:
-        return _anchors_at(lambda *a: lib().crdt_hip_replica_anchors_at_bytes(
-            self.ctx._h, self._h, *a), positions, bias, self.ctx._h, out)
-
-    def resolve_anchors_raw(self, anchors, out=None) -> np.ndarray:
-        return _anchors_resolve(lambda *a: lib().crdt_hip_replica_anchors_resolve(
-            self.ctx._h, self._h, *a), anchors, self.ctx._h, out)
-
-    def anchors_at(self, positions, bias=AFTER) -> list:
-        """OpLog.anchors_at on the device (crdt_hip_replica_anchors_at)."""
-        return _anchor_list(self.anchors_at_raw(positions, bias))
-
-    def anchors_at_bytes(self, positions, bias=AFTER) -> list:
-        """OpLog.anchors_at_bytes on the device (crdt_hip_replica_anchors_at_bytes)."""
-        return _anchor_list(self.anchors_at_bytes_raw(positions, bias))
-
-    def resolve_anchors(self, anchors) -> list:
-        """OpLog.resolve_anchors on the device (crdt_hip_replica_anchors_resolve)."""
-        return _anchor_pos_list(self.resolve_anchors_raw(anchors))
-
-    # Formats (crdt_hip.h, "formats"): the same arrays as OpLog.spans_raw, byte for byte, from HIP
-    # kernels over the kept document order.
-    def spans_raw(self, formats, out=None) -> tuple:
-        return _spans_get(lambda *a: lib().crdt_hip_replica_spans(self.ctx._h, self._h, *a), formats,
-                          self.ctx._h, out)
-
-    def spans(self, formats) -> tuple:
-        """OpLog.spans on the device (crdt_hip_replica_spans)."""
-        return _span_list(self.spans_raw(formats))
-
     def info(self) -> tuple:
         """(items, visible codepoints, visible UTF-8 bytes)."""
-        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().crdt_hip_replica_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return int(a.value), int(b.value), int(c.value)
+        return _outs(lambda *a: lib().crdt_hip_replica_info(self._h, *a), 3)
 
     def merge(self) -> tuple:
         """Merged document: (utf8 bytes, tree digest)."""
@@ -1454,33 +1299,107 @@ class Replica:
         """The downstream closure (main.rs:63-69) in one device call: a copy of this replica
         receives the whole resident batch and is merged; returns (codepoints, UTF-8 bytes, tree
         digest) and leaves this replica unchanged (crdt_hip_replica_replay)."""
-        c, n, d = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().crdt_hip_replica_replay(self.ctx._h, self._h, batch._h, C.byref(c),
-                                             C.byref(n), C.byref(d)), self.ctx._h)
-        return int(c.value), int(n.value), int(d.value)
+        return _outs(lambda *a: lib().crdt_hip_replica_replay(self.ctx._h, self._h, batch._h, *a), 3,
+                     self.ctx._h)
 
     def merge_len(self) -> tuple:
         """(codepoints, UTF-8 bytes, tree digest) of the merged document; the codepoints are
         counted on the device from the merged bytes (crdt_hip_replica_merge_len)."""
-        c, n, d = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(lib().crdt_hip_replica_merge_len(self.ctx._h, self._h, C.byref(c), C.byref(n),
-                                                C.byref(d)), self.ctx._h)
-        return int(c.value), int(n.value), int(d.value)
+        return _outs(lambda *a: lib().crdt_hip_replica_merge_len(self.ctx._h, self._h, *a), 3,
+                     self.ctx._h)
 
 
-class _RichText:
-    """Formats on an adapter (crdt_hip.h, "formats"): the adapter keeps its format ops in a dict by
-    op, makes their anchors where its document lies, and paints spans in its own unit.  Formats
-    travel beside the text, never in it: sync_formats_from is the union of two dicts."""
+class _Adapter:
+    """What HipMerge, HipDownstream and HipDownstreamBytes share: the reference's `Upstream` edits
+    (rope.rs:6-33), sync, marks, text windows, anchors and formats, all on _rt_peer(), the document
+    the adapter holds (an OpLog; for the device adapters the Replica, queued updates decoded first).
+    Positions, patches and lengths are in the adapter's unit, codepoints or, with
+    EDITS_USE_BYTE_OFFSETS, UTF-8 bytes (translated on the device: crdt_hip.h, "byte offsets").
 
+    Formats (crdt_hip.h, "formats"): the adapter keeps its format ops in a dict by op, makes their
+    anchors where its document lies, and paints spans in its own unit.  Formats travel beside the
+    text, never in it: sync_formats_from is the union of two dicts."""
+
+    EDITS_USE_BYTE_OFFSETS = False
     START, END = 1, 2  # `expand` bits: text typed at that edge of the range joins it
     agent = 0          # the low 16 bits of this peer's format ops (set_agent)
 
     def _rt_peer(self):  # what holds the document: an OpLog or a Replica, up to date
         raise NotImplementedError
 
+    # Upstream (rope.rs:6-33)
+    def insert(self, at: int, text: str) -> None:
+        doc = self._rt_peer()
+        (doc.insert_bytes if self.EDITS_USE_BYTE_OFFSETS else doc.insert)(at, text)
+
+    def remove(self, start: int, end: int) -> None:
+        doc = self._rt_peer()
+        (doc.remove_bytes if self.EDITS_USE_BYTE_OFFSETS else doc.remove)(start, end)
+
+    def replace(self, start: int, end: int, text: str) -> None:
+        doc = self._rt_peer()
+        (doc.replace_bytes if self.EDITS_USE_BYTE_OFFSETS else doc.replace)(start, end, text)
+
+    def merge_from(self, other) -> tuple:
+        """`Downstream for Automerge`'s apply_update(&mut self, other: &Self) = doc.merge(other)
+        (rope.rs:234-236): take every op of a divergent replica (join; both documents RGA or both
+        Fugue)."""
+        return self._rt_peer().join(other._rt_peer())
+
+    def sync_from(self, other) -> tuple:
+        """The Yrs Downstream (rope.rs:252-255): state_vector(), the other's encode_diff against
+        it, apply_update.  Takes what this document lacks of a divergent replica without moving the
+        other's whole log.  Returns (items appended, items tombstoned, delta bytes)."""
+        doc = self._rt_peer()
+        delta = other._rt_peer().encode_diff(doc.state_vector())
+        return doc.apply_diff(delta) + (len(delta),)
+
+    def mark(self) -> Mark:
+        """Remember this version of the document."""
+        return self._rt_peer().mark()
+
+    def patches_since(self, mark: Mark) -> list:
+        """What changed since `mark` as [(pos, del, ins)], the reference's TestPatch applied as
+        Upstream::replace (rope.rs:21-32): what an editor that keeps a text buffer beside this
+        adapter applies to it after a remote change."""
+        doc = self._rt_peer()
+        return (doc.patches_since_bytes if self.EDITS_USE_BYTE_OFFSETS else doc.patches_since)(mark)
+
+    def sync_patches(self, other) -> list:
+        """mark, sync_from(other), patches_since: the other's changes as positional edits."""
+        m = self.mark()
+        try:
+            self.sync_from(other)
+            return self.patches_since(m)
+        finally:
+            m.close()
+
+    def text_range(self, start: int, end: int = None) -> str:
+        """Window [start, end) of the document now: what an editor paints (a device adapter gets
+        only the window back)."""
+        return self.text_at(None, start, end)
+
+    def text_at(self, mark: Mark, start: int = 0, end: int = None) -> str:
+        """The document as of `mark`, or window [start, end) of it: history without a saved copy of
+        the text."""
+        return self._rt_peer().text_at(mark, start, end, self.EDITS_USE_BYTE_OFFSETS).decode("utf-8")
+
     def _rt_anchors(self, positions, bias) -> list:
-        return self._rt_peer().anchors_at(positions, bias)
+        doc = self._rt_peer()
+        return (doc.anchors_at_bytes if self.EDITS_USE_BYTE_OFFSETS else doc.anchors_at)(positions, bias)
+
+    def anchor_at(self, pos: int, bias: int = AFTER) -> tuple:
+        """A cursor at gap `pos` as (id, bias): a place that survives every later edit and sync and
+        means the same on every peer."""
+        return self._rt_anchors([pos], bias)[0]
+
+    def resolve_many(self, anchors) -> list:
+        """Where each anchor lies now; None for one whose item this document does not hold yet."""
+        unit = 1 if self.EDITS_USE_BYTE_OFFSETS else 0
+        return [None if p[2] == UNKNOWN else p[unit] for p in self._rt_peer().resolve_anchors(anchors)]
+
+    def resolve(self, anchor: tuple):
+        return self.resolve_many([anchor])[0]
 
     def set_agent(self, agent: int) -> None:
         """This peer's agent id, for its later text edits and its later format ops alike."""
@@ -1520,19 +1439,16 @@ class _RichText:
         self.formats.update(new)
         return len(new)
 
-    def _rt_unit(self, span: tuple) -> tuple:
-        pos, ln, _, _, attrs = span
-        return pos, ln, attrs
-
     def spans(self) -> tuple:
         """([(pos, len, {key: value})] in this adapter's unit, pending): what an editor paints,
         and the formats whose anchors this peer cannot place until its next text sync."""
         sp, pend = self._rt_peer().spans(
             [(f[0], f[1], f[2], f[3], op, f[4]) for op, f in sorted(self.formats.items())])
-        return [self._rt_unit(x) for x in sp], pend
+        unit = 2 if self.EDITS_USE_BYTE_OFFSETS else 0  # (pos, len, pos_bytes, len_bytes, attrs)
+        return [(x[unit], x[unit + 1], x[4]) for x in sp], pend
 
 
-class HipMerge(_RichText):
+class HipMerge(_Adapter):
     """Mirror of the reference's per-CRDT adapter for the GPU engine.
 
     `Upstream` (/root/reference/src/rope.rs:6-33): NAME, EDITS_USE_BYTE_OFFSETS, from_str,
@@ -1542,11 +1458,13 @@ class HipMerge(_RichText):
     """
 
     NAME = "mi355x"
-    EDITS_USE_BYTE_OFFSETS = False
     _ctx: Context | None = None
 
     def __init__(self, log: OpLog):
         self.log = log
+
+    def _rt_peer(self) -> OpLog:
+        return self.log
 
     @classmethod
     def context(cls) -> Context:
@@ -1560,15 +1478,6 @@ class HipMerge(_RichText):
         if s:
             log.insert(0, s)
         return cls(log)
-
-    def insert(self, at: int, text: str) -> None:
-        self.log.insert(at, text)
-
-    def remove(self, start: int, end: int) -> None:
-        self.log.remove(start, end)
-
-    def replace(self, start: int, end: int, text: str) -> None:
-        self.log.replace(start, end, text)
 
     def clone(self) -> "HipMerge":
         return HipMerge(self.log.clone())
@@ -1596,81 +1505,27 @@ class HipMerge(_RichText):
     def apply_update(self, update: bytes) -> None:
         self.log.apply_update(update)
 
-    def merge_from(self, other: "HipMerge") -> tuple:
-        """`Downstream for Automerge`'s apply_update(&mut self, other: &Self) = doc.merge(other)
-        (rope.rs:234-236): take every op of a divergent replica (OpLog.join; both logs RGA or
-        both Fugue)."""
-        return self.log.join(other.log)
 
-    def sync_from(self, other: "HipMerge") -> tuple:
-        """The Yrs Downstream (rope.rs:252-255): state_vector(), the other's encode_diff against
-        it, apply_update.  Takes what this log lacks of a divergent replica without moving the
-        other's whole log.  Returns (items appended, items tombstoned, delta bytes)."""
-        delta = other.log.encode_diff(self.log.state_vector())
-        return self.log.apply_diff(delta) + (len(delta),)
-
-    def mark(self) -> Mark:
-        """Remember this version of the document (OpLog.mark)."""
-        return self.log.mark()
-
-    def patches_since(self, mark: Mark) -> list:
-        """What changed since `mark` as [(pos, del, ins)], the reference's TestPatch applied as
-        Upstream::replace (rope.rs:21-32): what an editor that keeps a text buffer beside this
-        adapter applies to it after a remote change."""
-        return self.log.patches_since(mark)
-
-    def sync_patches(self, other: "HipMerge") -> list:
-        """mark, sync_from(other), patches_since: the other's changes as positional edits."""
-        m = self.mark()
-        try:
-            self.sync_from(other)
-            return self.patches_since(m)
-        finally:
-            m.close()
-
-    def text_range(self, start: int, end: int = None) -> str:
-        """Window [start, end) of the document now, in the adapter's unit (OpLog.text_at): what an
-        editor paints."""
-        return self.text_at(None, start, end)
-
-    def text_at(self, mark: Mark, start: int = 0, end: int = None) -> str:
-        """The document as of `mark`, or window [start, end) of it (OpLog.text_at): history without
-        a saved copy of the text."""
-        return self.log.text_at(mark, start, end, self.EDITS_USE_BYTE_OFFSETS).decode("utf-8")
-
-    def anchor_at(self, pos: int, bias: int = AFTER) -> tuple:
-        """A cursor at gap `pos` as (id, bias): a place that survives every later edit and sync and
-        means the same on every peer (OpLog.anchors_at)."""
-        return self.log.anchors_at([pos], bias)[0]
-
-    def resolve_many(self, anchors) -> list:
-        """Where each anchor lies now; None for one whose item this log does not hold yet."""
-        return [None if st == UNKNOWN else pos for pos, _, st in self.log.resolve_anchors(anchors)]
-
-    def resolve(self, anchor: tuple):
-        return self.resolve_many([anchor])[0]
-
-    def _rt_peer(self) -> OpLog:
-        return self.log
-
-
-class HipDownstream(_RichText):
+class HipDownstream(_Adapter):
     """`Downstream` (/root/reference/src/rope.rs:185-191) with the replica on the device.
 
     apply_update() queues the encoded update on the host; len() decodes every queued update on
     the device in one batch (crdt_hip_replica_apply_updates), merges the replica there and
-    returns its visible codepoints.  clone() copies the replica device to device.  It is an
-    `Upstream` (rope.rs:6-33) too: from_str, insert, remove and replace resolve the edit on the
-    device (crdt_hip_replica_replace), so no host log is kept beside the replica.  This is the
-    shape of the Rust adapter in INTEGRATION.md.
+    returns its visible codepoints; every other call decodes the queue first too.  clone() copies
+    the replica device to device.  It is an `Upstream` (rope.rs:6-33) too: from_str, insert, remove
+    and replace resolve the edit on the device (crdt_hip_replica_replace), so no host log is kept
+    beside the replica.  This is the shape of the Rust adapter in INTEGRATION.md.
     """
 
     NAME = "mi355x-device"
-    EDITS_USE_BYTE_OFFSETS = False
 
     def __init__(self, replica: Replica):
         self.replica = replica
         self.pending: list = []
+
+    def _rt_peer(self) -> Replica:
+        self.flush()
+        return self.replica
 
     @classmethod
     def upstream_updates(cls, start_content: str, patches) -> tuple:
@@ -1678,26 +1533,12 @@ class HipDownstream(_RichText):
         ctx = HipMerge.context()
         return cls(Replica(ctx, up.log if up.log.view().n else None)), updates
 
-    # Upstream (rope.rs:6-33) on the device: the queued updates are decoded first, then the edit
-    # is resolved against the replica where it lies (Replica.replace); no host log is kept
     @classmethod
     def from_str(cls, s: str) -> "HipDownstream":
         d = cls(Replica(HipMerge.context()))
         if s:
             d.insert(0, s)
         return d
-
-    def insert(self, at: int, text: str) -> None:
-        self.flush()
-        self.replica.insert(at, text)
-
-    def remove(self, start: int, end: int) -> None:
-        self.flush()
-        self.replica.remove(start, end)
-
-    def replace(self, start: int, end: int, text: str) -> None:
-        self.flush()
-        self.replica.replace(start, end, text)
 
     def clone(self) -> "HipDownstream":
         c = HipDownstream(self.replica.clone())
@@ -1712,84 +1553,19 @@ class HipDownstream(_RichText):
             self.replica.apply_updates(self.pending)
             self.pending = []
 
-    def merge_from(self, other: "HipDownstream") -> tuple:
-        """doc.merge(other) (rope.rs:234-236) on the device: both replicas decode their queued
-        updates, then this one takes every item of the other (Replica.join; both replicas RGA or
-        both Fugue)."""
-        self.flush()
-        other.flush()
-        return self.replica.join(other.replica)
-
-    def sync_from(self, other: "HipDownstream") -> tuple:
-        """HipMerge.sync_from on the device: both replicas decode their queued updates, then this
-        one applies the other's delta against its state vector.  Returns (items appended, items
-        tombstoned, delta bytes)."""
-        self.flush()
-        other.flush()
-        delta = other.replica.encode_diff(self.replica.state_vector())
-        return self.replica.apply_diff(delta) + (len(delta),)
-
-    def mark(self) -> Mark:
-        """Remember this version of the document: the queued updates are decoded first
-        (Replica.mark)."""
-        self.flush()
-        return self.replica.mark()
-
-    def patches_since(self, mark: Mark) -> list:
-        """HipMerge.patches_since on the device: the queued updates are decoded first."""
-        self.flush()
-        return self.replica.patches_since(mark)
-
-    def sync_patches(self, other: "HipDownstream") -> list:
-        """mark, sync_from(other), patches_since: the other's changes as positional edits."""
-        m = self.mark()
-        try:
-            self.sync_from(other)
-            return self.patches_since(m)
-        finally:
-            m.close()
-
-    def text_range(self, start: int, end: int = None) -> str:
-        """HipMerge.text_range on the device: the queued updates are decoded first, and only the
-        window comes back (Replica.text_at; positions in the adapter's unit)."""
-        return self.text_at(None, start, end)
-
-    def text_at(self, mark: Mark, start: int = 0, end: int = None) -> str:
-        """HipMerge.text_at on the device: the queued updates are decoded first."""
-        self.flush()
-        return self.replica.text_at(mark, start, end, self.EDITS_USE_BYTE_OFFSETS).decode("utf-8")
-
-    def anchor_at(self, pos: int, bias: int = AFTER) -> tuple:
-        """HipMerge.anchor_at on the device: the queued updates are decoded first."""
-        self.flush()
-        return self.replica.anchors_at([pos], bias)[0]
-
-    def resolve_many(self, anchors) -> list:
-        """HipMerge.resolve_many on the device: the queued updates are decoded first."""
-        self.flush()
-        return [None if st == UNKNOWN else pos
-                for pos, _, st in self.replica.resolve_anchors(anchors)]
-
-    def resolve(self, anchor: tuple):
-        return self.resolve_many([anchor])[0]
-
-    def _rt_peer(self) -> Replica:
-        self.flush()
-        return self.replica
-
     def text(self) -> str:
-        self.flush()
-        return self.replica.merge()[0].decode("utf-8")
+        return self._rt_peer().merge()[0].decode("utf-8")
 
     def len(self) -> int:
-        """Codepoints of the merged document (main.rs:68 asserts them): the merge's own count,
-        cross-checked against the decoder's visible-codepoint counter."""
-        self.flush()
-        cps, _, _ = self.replica.merge_len()
-        counter = self.replica.info()[1]
-        if cps != counter:
-            raise CrdtHipError(-5, f"merged text has {cps} codepoints, the decoder counted {counter}")
-        return cps
+        """The merged document's length in the adapter's unit (main.rs:68 asserts it): the merge's
+        own count, cross-checked against the decoder's visible counter."""
+        doc = self._rt_peer()
+        unit = 1 if self.EDITS_USE_BYTE_OFFSETS else 0
+        n, counter = doc.merge_len()[unit], doc.info()[1 + unit]
+        if n != counter:
+            raise CrdtHipError(-5, f"merged text has {n} {('codepoints', 'bytes')[unit]}, "
+                                   f"the decoder counted {counter}")
+        return n
 
 
 class HipDownstreamBytes(HipDownstream):
@@ -1801,49 +1577,7 @@ class HipDownstreamBytes(HipDownstream):
     NAME = "mi355x-device-bytes"
     EDITS_USE_BYTE_OFFSETS = True
 
-    def insert(self, at: int, text: str) -> None:
-        self.flush()
-        self.replica.insert_bytes(at, text)
-
-    def remove(self, start: int, end: int) -> None:
-        self.flush()
-        self.replica.remove_bytes(start, end)
-
-    def replace(self, start: int, end: int, text: str) -> None:
-        self.flush()
-        self.replica.replace_bytes(start, end, text)
-
     def clone(self) -> "HipDownstreamBytes":
         c = HipDownstreamBytes(self.replica.clone())
         c.pending = list(self.pending)
         return c
-
-    def patches_since(self, mark: Mark) -> list:
-        self.flush()
-        return self.replica.patches_since_bytes(mark)
-
-    def anchor_at(self, pos: int, bias: int = AFTER) -> tuple:
-        self.flush()
-        return self.replica.anchors_at_bytes([pos], bias)[0]
-
-    def resolve_many(self, anchors) -> list:
-        self.flush()
-        return [None if st == UNKNOWN else nbytes
-                for _, nbytes, st in self.replica.resolve_anchors(anchors)]
-
-    def _rt_anchors(self, positions, bias) -> list:
-        return self._rt_peer().anchors_at_bytes(positions, bias)
-
-    def _rt_unit(self, span: tuple) -> tuple:
-        _, _, pos, ln, attrs = span
-        return pos, ln, attrs
-
-    def len(self) -> int:
-        """UTF-8 bytes of the merged document: the merge's own count, cross-checked against the
-        decoder's visible-byte counter."""
-        self.flush()
-        _, nbytes, _ = self.replica.merge_len()
-        counter = self.replica.info()[2]
-        if nbytes != counter:
-            raise CrdtHipError(-5, f"merged text has {nbytes} bytes, the decoder counted {counter}")
-        return nbytes

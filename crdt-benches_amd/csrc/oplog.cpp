@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "crdt_hip.h"
+#include "trace.hpp"
 #include "util.hpp"
 
 namespace crdt {
@@ -361,13 +362,13 @@ std::string OpLog::remove_rga(uint64_t start, uint64_t end) {
 // remove_rga + insert_rga, fused: every column is sized once to the trace's bound and written by
 // index (no per-item push_back), a one-byte insert (typing) and a one-codepoint delete
 // (backspace) take straight-line paths, and no std::string is made per patch.
-std::string OpLog::replay(const uint64_t* pt, size_t np, const char* ins, size_t ins_total) {
+std::string OpLog::replay(const Patch* pt, size_t np, const char* ins, size_t ins_total) {
     if (fugue || stale_) {
         for (size_t i = 0; i < np; ++i) {
-            const uint64_t* q = pt + 4 * i;
+            const Patch& q = pt[i];
             std::string e;
-            if (q[1]) e = remove(q[0], q[0] + q[1]);
-            if (e.empty() && q[3]) e = insert_utf8(q[0], ins + q[2], q[3]);
+            if (q.del) e = remove(q.pos, q.pos + q.del);
+            if (e.empty() && q.ins_len) e = insert_utf8(q.pos, ins + q.ins_off, q.ins_len);
             if (!e.empty()) return e;
         }
         return "";
@@ -431,7 +432,7 @@ std::string OpLog::replay(const uint64_t* pt, size_t np, const char* ins, size_t
     };
     const char* err = nullptr;
     for (size_t i = 0; i < np && !err; ++i) {
-        const uint64_t pos = pt[4 * i], del = pt[4 * i + 1], ioff = pt[4 * i + 2], ilen = pt[4 * i + 3];
+        const uint64_t pos = pt[i].pos, del = pt[i].del, ioff = pt[i].ins_off, ilen = pt[i].ins_len;
         if (del) {  // (remove_rga)
             if (pos + del > nvis) {
                 err = "remove range out of range";

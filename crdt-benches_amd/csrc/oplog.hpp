@@ -18,6 +18,8 @@
 
 namespace crdt {
 
+struct Patch;  // trace.hpp
+
 // Op-log columns: vectors whose growth leaves new elements default-initialised (uninitialised
 // for these integer types) instead of zero-filled: the resolver sizes every column once to the
 // trace's bound and writes each item by index (OpLog::replay), so a zero fill would be a second
@@ -222,11 +224,11 @@ public:
     std::string remove(uint64_t start, uint64_t end);
 
     // The upstream loop of one editing trace (main.rs:28-36: replace = remove then insert per
-    // patch, rope.rs:21-32) as one call: patches as (pos, del, ins_off, ins_len) in codepoints,
+    // patch, rope.rs:21-32) as one call: a trace's patches (trace.hpp: pos and del in codepoints),
     // ins the concatenated inserted UTF-8 (ins_total bytes: every patch's text lies inside).
     // RGA logs run a fused loop over columns sized once; Fugue (or stale) logs take insert /
     // remove per patch.  "" or an error message.
-    std::string replay(const uint64_t* patches, size_t n, const char* ins, size_t ins_total);
+    std::string replay(const Patch* patches, size_t n, const char* ins, size_t ins_total);
 
     // Downstream wire format (see oplog.cpp for the layout).
     uint64_t version() const { return ((uint64_t)size() << 32) | (uint32_t)del_ops.size(); }
