@@ -798,6 +798,97 @@ LogMark OpLog::mark() const {
     return m;
 }
 
+// ---- what the views below share, each rule once (`order`: the log's document_order) -------------
+namespace {
+// A version of the log: now (m null) or at a mark.  The host counterparts of mark_fits
+// (replica.hpp) and of SelNow / SelMark (order.hpp).
+int mark_check(const OpLog& log, const LogMark* m, std::string& err) {
+    if (m && (log.size() < m->n || m->deleted.size() != m->n)) {
+        err = "the log holds fewer items than the mark";
+        return CRDT_HIP_EINVAL;
+    }
+    return CRDT_HIP_OK;
+}
+bool in_version(const OpLog& log, const LogMark* m, uint32_t id) {
+    return m ? id <= m->n && !m->deleted[id - 1] : !log.deleted[id - 1];
+}
+
+// ends[v]: UTF-8 bytes of the first v visible items of `ids` (the order, or its visible items), the
+// only byte offsets that lie inside no codepoint; byte_rank: the v with ends[v] == b, or false.
+std::vector<uint64_t> byte_ends(const OpLog& log, const std::vector<uint32_t>& ids) {
+    std::vector<uint64_t> ends;
+    ends.reserve((size_t)log.visible() + 1);
+    ends.push_back(0);
+    for (uint32_t id : ids)
+        if (!log.deleted[id - 1]) ends.push_back(ends.back() + utf8_len_cp(log.cp[id - 1]));
+    return ends;
+}
+bool byte_rank(const std::vector<uint64_t>& ends, uint64_t b, uint64_t& v) {
+    const auto it = std::lower_bound(ends.begin(), ends.end(), b);
+    if (it == ends.end() || *it != b) return false;
+    v = (uint64_t)(it - ends.begin());
+    return true;
+}
+
+constexpr uint32_t kNoGap = ~0u;
+// The identities a call's anchors name and where the log holds them (locate.hpp on the device).
+struct Located {
+    std::vector<uint64_t> want;  // the identities asked for; find() leaves them sorted and distinct
+    std::vector<uint32_t> rank;  // per identity the rank, 1-based, of the slot that holds it (0: none)
+    void ask(const AnchorRec& a) {
+        if (a.id != kAnchorEdge) want.push_back(a.id);
+    }
+    size_t index(uint64_t ident) const {  // of an identity in `want`, or where it would be
+        return (size_t)(std::lower_bound(want.begin(), want.end(), ident) - want.begin());
+    }
+    // One scan of the log; of two slots of a malformed log that share an identity, the lower wins.
+    void find(const OpLog& log, const std::vector<uint32_t>& order) {
+        std::sort(want.begin(), want.end());
+        want.erase(std::unique(want.begin(), want.end()), want.end());
+        rank.assign(want.size(), 0u);
+        if (want.empty()) return;
+        const uint32_t n = log.size();
+        Column<uint32_t> rk(n + 1ull);  // slot -> rank (the order names every slot)
+        for (uint32_t k = 0; k < n; ++k) rk[order[k]] = k + 1;
+        for (uint32_t id = 1; id <= n; ++id) {  // (in slot order: the identities mostly ascend)
+            const uint64_t ident = log.ident(id);
+            const size_t j = index(ident);
+            if (j < want.size() && want[j] == ident && !rank[j]) rank[j] = rk[id];
+        }
+    }
+    // The gap an anchor names among the n items in document order (gap g lies right after rank g,
+    // gap 0 at the document start), or kNoGap: no item holds its identity.
+    uint32_t gap(const AnchorRec& a, uint32_t n) const {
+        if (a.id == kAnchorEdge) return a.bias == kAnchorAfter ? 0u : n;
+        const uint32_t r = rank[index(a.id)];
+        return !r ? kNoGap : a.bias == kAnchorAfter ? r : r - 1;
+    }
+};
+
+// The visible codepoints and their UTF-8 bytes before each of `gaps`, which leave sorted and
+// distinct (view_walk, view.hpp, on the device).
+void visible_before(const OpLog& log, const std::vector<uint32_t>& order, std::vector<uint32_t>& gaps,
+                    std::vector<uint64_t>& vis, std::vector<uint64_t>& visb) {
+    std::sort(gaps.begin(), gaps.end());
+    gaps.erase(std::unique(gaps.begin(), gaps.end()), gaps.end());
+    vis.resize(gaps.size());
+    visb.resize(gaps.size());
+    uint64_t v = 0, vb = 0;
+    size_t j = 0;
+    for (uint32_t k = 0; k <= order.size() && j < gaps.size(); ++k) {
+        if (k && !log.deleted[order[k - 1] - 1]) {
+            ++v;
+            vb += utf8_len_cp(log.cp[order[k - 1] - 1]);
+        }
+        if (gaps[j] == k) {
+            vis[j] = v;
+            visb[j] = vb;
+            ++j;
+        }
+    }
+}
+}  // namespace
+
 int OpLog::patches_since(const LogMark& m, std::vector<PatchRec>& out, std::vector<uint8_t>& ins,
                          std::string& err) const {
     return patches_walk(m, false, out, ins, err);
@@ -813,10 +904,7 @@ int OpLog::patches_walk(const LogMark& m, bool bytes, std::vector<PatchRec>& out
                         std::vector<uint8_t>& ins, std::string& err) const {
     out.clear();
     ins.clear();
-    if (size() < m.n || m.deleted.size() != m.n) {
-        err = "the log holds fewer items than the mark";
-        return CRDT_HIP_EINVAL;
-    }
+    if (int rc = mark_check(*this, &m, err)) return rc;
     std::vector<uint32_t> order;
     err = document_order(order);
     if (!err.empty()) return CRDT_HIP_EBADLOG;
@@ -824,7 +912,7 @@ int OpLog::patches_walk(const LogMark& m, bool bytes, std::vector<PatchRec>& out
     uint64_t del = 0;   // what the open run deletes
     bool open = false;  // the previous K, D or I item was a D or an I: its run goes on
     for (uint32_t id : order) {
-        const bool was = id <= m.n && !m.deleted[id - 1], now = !deleted[id - 1];
+        const bool was = in_version(*this, &m, id), now = in_version(*this, nullptr, id);
         if (!was && !now) continue;
         const uint64_t w = bytes ? utf8_len_cp(cp[id - 1]) : 1;
         if (was && now) {
@@ -901,19 +989,13 @@ int text_check_window(uint64_t start, uint64_t end, uint64_t total, bool inside,
 
 int OpLog::text_at(const LogMark* m, uint64_t start, uint64_t end, uint32_t flags, uint8_t* out,
                    size_t cap, size_t* out_len, TextInfo* info, std::string& err) const {
-    if (m && (size() < m->n || m->deleted.size() != m->n)) {
-        err = "the log holds fewer items than the mark";
-        return CRDT_HIP_EINVAL;
-    }
+    if (int rc = mark_check(*this, m, err)) return rc;
     int rc = text_check(start, end, flags, out_len, err);
     if (rc) return rc;
     const bool bytes = (flags & kTextBytes) != 0;
     std::vector<uint32_t> order;
     err = document_order(order);
     if (!err.empty()) return CRDT_HIP_EBADLOG;
-    auto selected = [&](uint32_t id) {
-        return m ? id <= m->n && !m->deleted[id - 1] : !deleted[id - 1];
-    };
     // one walk: the totals, and each boundary where the unit's running count meets it (a gap
     // between two selected items, the start or the end of the version)
     TextInfo w{};
@@ -933,7 +1015,7 @@ int OpLog::text_at(const LogMark* m, uint64_t start, uint64_t end, uint32_t flag
         }
     };
     for (uint32_t id : order) {
-        if (!selected(id)) continue;
+        if (!in_version(*this, m, id)) continue;
         gap();
         ++c;
         b += utf8_len_cp(cp[id - 1]);
@@ -950,7 +1032,7 @@ int OpLog::text_at(const LogMark* m, uint64_t start, uint64_t end, uint32_t flag
     uint64_t k = 0;  // selected items so far
     uint8_t* o = out;
     for (uint32_t id : order) {
-        if (!selected(id)) continue;
+        if (!in_version(*this, m, id)) continue;
         if (k >= w.start + w.n) break;
         if (k++ < w.start) continue;
         o += utf8_put(cp[id - 1], reinterpret_cast<char*>(o));
@@ -999,44 +1081,25 @@ int OpLog::anchors_at(const uint64_t* pos, const uint8_t* bias, size_t n, bool b
     std::vector<uint32_t> order;
     err = document_order(order);
     if (!err.empty()) return CRDT_HIP_EBADLOG;
-    // vis[v - 1]: the v-th visible item; ends[v]: UTF-8 bytes of the first v visible items
-    std::vector<uint32_t> vis;
-    std::vector<uint64_t> ends;
+    std::vector<uint32_t> vis;  // vis[v - 1]: the v-th visible item
     vis.reserve((size_t)nvis_);
-    if (bytes) {
-        ends.reserve((size_t)nvis_ + 1);
-        ends.push_back(0);
-    }
-    for (uint32_t id : order) {
-        if (deleted[id - 1]) continue;
-        vis.push_back(id);
-        if (bytes) ends.push_back(ends.back() + utf8_len_cp(cp[id - 1]));
-    }
+    for (uint32_t id : order)
+        if (!deleted[id - 1]) vis.push_back(id);
+    const std::vector<uint64_t> ends = bytes ? byte_ends(*this, vis) : std::vector<uint64_t>();
     std::vector<AnchorRec> res(n);
     for (size_t k = 0; k < n; ++k) {
         uint64_t v = pos[k];  // visible items before the gap
-        if (bytes) {
-            const auto it = std::lower_bound(ends.begin(), ends.end(), v);
-            if (it == ends.end() || *it != v) {
-                err = "anchor position inside a codepoint";
-                return CRDT_HIP_EINVAL;
-            }
-            v = (uint64_t)(it - ends.begin());
+        if (bytes && !byte_rank(ends, pos[k], v)) {
+            err = "anchor position inside a codepoint";
+            return CRDT_HIP_EINVAL;
         }
         const uint32_t b = bias ? bias[k] : kAnchorAfter;
         const uint64_t item = b == kAnchorAfter ? v : v + 1;  // 1-based visible rank (0, len + 1: edge)
-        if (item > vis.size()) {
-            if (b == kAnchorAfter) {  // (anchor_check_at against a counter the log does not bear out)
-                err = "the visible items disagree with the log's counter";
-                return CRDT_HIP_EBADLOG;
-            }
-            res[k] = AnchorRec{kAnchorEdge, b, 0u};
-        } else if (item == 0) {
-            res[k] = AnchorRec{kAnchorEdge, b, 0u};
-        } else {
-            const uint32_t id = vis[item - 1];
-            res[k] = AnchorRec{((uint64_t)lamport[id - 1] << 16) | agent[id - 1], b, 0u};
+        if (item > vis.size() && b == kAnchorAfter) {  // (the log does not bear out its counter)
+            err = "the visible items disagree with the log's counter";
+            return CRDT_HIP_EBADLOG;
         }
+        res[k] = AnchorRec{item == 0 || item > vis.size() ? kAnchorEdge : ident(vis[item - 1]), b, 0u};
     }
     std::memcpy(out, res.data(), n * sizeof(AnchorRec));
     return CRDT_HIP_OK;
@@ -1048,55 +1111,28 @@ int OpLog::anchors_resolve(const AnchorRec* a, size_t n, AnchorPosRec* out, std:
     std::vector<uint32_t> order;
     err = document_order(order);
     if (!err.empty()) return CRDT_HIP_EBADLOG;
-    // the distinct identities asked for, sorted, and the slot that holds each (0: none; of two
-    // slots of a malformed log that share an identity, the lower)
-    std::vector<uint64_t> want;
-    want.reserve(n);
-    for (size_t k = 0; k < n; ++k)
-        if (a[k].id != kAnchorEdge) want.push_back(a[k].id);
-    std::sort(want.begin(), want.end());
-    want.erase(std::unique(want.begin(), want.end()), want.end());
-    std::vector<uint32_t> slot(want.size(), 0u);
-    if (!want.empty())
-        for (uint32_t id = 1; id <= size(); ++id) {
-            const uint64_t ident = ((uint64_t)lamport[id - 1] << 16) | agent[id - 1];
-            const auto it = std::lower_bound(want.begin(), want.end(), ident);
-            if (it != want.end() && *it == ident && !slot[it - want.begin()]) slot[it - want.begin()] = id;
-        }
-    // per wanted slot: the visible items, and their bytes, at the ranks before it
-    std::vector<uint64_t> before(want.size(), 0), before_b(want.size(), 0);
-    std::vector<uint32_t> at(size() + 1ull, ~0u);  // slot -> its index in `want`
-    for (size_t j = 0; j < want.size(); ++j)
-        if (slot[j]) at[slot[j]] = (uint32_t)j;
-    uint64_t v = 0, vb = 0;
-    for (uint32_t id : order) {
-        if (at[id] != ~0u) {
-            before[at[id]] = v;
-            before_b[at[id]] = vb;
-        }
-        if (!deleted[id - 1]) {
-            ++v;
-            vb += utf8_len_cp(cp[id - 1]);
-        }
+    Located l;
+    l.want.reserve(n);
+    for (size_t k = 0; k < n; ++k) l.ask(a[k]);
+    l.find(*this, order);
+    std::vector<uint32_t> at(n), gaps;  // the gap each anchor names, and the gaps named
+    for (size_t k = 0; k < n; ++k) {
+        at[k] = l.gap(a[k], size());
+        if (at[k] != kNoGap) gaps.push_back(at[k]);
     }
+    std::vector<uint64_t> vis, visb;
+    visible_before(*this, order, gaps, vis, visb);
     std::vector<AnchorPosRec> res(n);
     for (size_t k = 0; k < n; ++k) {
-        if (a[k].id == kAnchorEdge) {
-            res[k] = a[k].bias == kAnchorAfter ? AnchorPosRec{0, 0, kAnchorLive, 0u}
-                                               : AnchorPosRec{v, vb, kAnchorLive, 0u};
-            continue;
-        }
-        const size_t j = (size_t)(std::lower_bound(want.begin(), want.end(), a[k].id) - want.begin());
-        const uint32_t id = slot[j];
-        if (!id) {
+        const uint32_t g = at[k];
+        if (g == kNoGap) {
             res[k] = AnchorPosRec{0, 0, kAnchorUnknown, 0u};
             continue;
         }
-        const bool live = !deleted[id - 1];
-        const bool add = live && a[k].bias == kAnchorAfter;
-        res[k] = AnchorPosRec{before[j] + (add ? 1u : 0u),
-                              before_b[j] + (add ? utf8_len_cp(cp[id - 1]) : 0u),
-                              live ? kAnchorLive : kAnchorDead, 0u};
+        // (a dead item counts nothing: the gaps on either side of it lie at one position)
+        const bool dead = a[k].id != kAnchorEdge && deleted[order[a[k].bias == kAnchorAfter ? g - 1 : g] - 1];
+        const size_t j = (size_t)(std::lower_bound(gaps.begin(), gaps.end(), g) - gaps.begin());
+        res[k] = AnchorPosRec{vis[j], visb[j], dead ? kAnchorDead : kAnchorLive, 0u};
     }
     std::memcpy(out, res.data(), n * sizeof(AnchorPosRec));
     return CRDT_HIP_OK;
@@ -1148,71 +1184,28 @@ int OpLog::spans(const FormatRec* f, size_t n, std::vector<SpanRec>& out, std::v
     err = document_order(order);
     if (!err.empty()) return CRDT_HIP_EBADLOG;
     const uint32_t N = size();
-    // the distinct identities the anchors name, sorted, and the rank of the slot that holds each
-    // (0: none; of two slots of a malformed log that share an identity, the lower)
-    std::vector<uint64_t> want;
-    want.reserve(2 * n);
+    Located l;
+    l.want.reserve(2 * n);
     for (size_t k = 0; k < n; ++k) {
-        if (f[k].start.id != kAnchorEdge) want.push_back(f[k].start.id);
-        if (f[k].end.id != kAnchorEdge) want.push_back(f[k].end.id);
+        l.ask(f[k].start);
+        l.ask(f[k].end);
     }
-    std::sort(want.begin(), want.end());
-    want.erase(std::unique(want.begin(), want.end()), want.end());
-    std::vector<uint32_t> rank_of(want.size(), 0u);
-    if (!want.empty()) {
-        std::vector<uint32_t> rk(N + 1ull, 0u);  // slot -> rank
-        for (uint32_t k = 0; k < N; ++k) rk[order[k]] = k + 1;
-        for (uint32_t id = 1; id <= N; ++id) {
-            const uint64_t ident = ((uint64_t)lamport[id - 1] << 16) | agent[id - 1];
-            const auto it = std::lower_bound(want.begin(), want.end(), ident);
-            if (it != want.end() && *it == ident && !rank_of[it - want.begin()]) rank_of[it - want.begin()] = rk[id];
-        }
-    }
+    l.find(*this, order);
     // per format its two gaps (a format that covers nothing: 1, 0), and the gaps that bound a range
-    auto gap = [&](const AnchorRec& a, uint32_t& g) {
-        if (a.id == kAnchorEdge) {
-            g = a.bias == kAnchorAfter ? 0u : N;
-            return true;
-        }
-        const uint32_t r = rank_of[std::lower_bound(want.begin(), want.end(), a.id) - want.begin()];
-        g = a.bias == kAnchorAfter ? r : r - 1;
-        return r != 0;
-    };
-    std::vector<uint32_t> gs(n), ge(n), bound;
+    std::vector<uint32_t> gs(n, 1u), ge(n, 0u), bound;
     for (size_t k = 0; k < n; ++k) {
-        uint32_t s = 0, e = 0;
-        const bool ks = gap(f[k].start, s), ke = gap(f[k].end, e);
-        if (!ks || !ke) ++pending;
-        if (ks && ke && s < e) {
+        const uint32_t s = l.gap(f[k].start, N), e = l.gap(f[k].end, N);
+        if (s == kNoGap || e == kNoGap) {
+            ++pending;
+        } else if (s < e) {
             gs[k] = s;
             ge[k] = e;
             bound.push_back(s);
             bound.push_back(e);
-        } else {
-            gs[k] = 1;
-            ge[k] = 0;
         }
     }
-    std::sort(bound.begin(), bound.end());
-    bound.erase(std::unique(bound.begin(), bound.end()), bound.end());
-    if (bound.size() < 2) return CRDT_HIP_OK;
-    // the visible codepoints and bytes at the ranks up to each boundary
-    std::vector<uint64_t> vis(bound.size()), visb(bound.size());
-    {
-        uint64_t v = 0, vb = 0;
-        size_t j = 0;
-        for (uint32_t k = 0; k <= N && j < bound.size(); ++k) {  // k: a gap, right after rank k
-            if (k && !deleted[order[k - 1] - 1]) {
-                ++v;
-                vb += utf8_len_cp(cp[order[k - 1] - 1]);
-            }
-            if (bound[j] == k) {
-                vis[j] = v;
-                visb[j] = vb;
-                ++j;
-            }
-        }
-    }
+    std::vector<uint64_t> vis, visb;  // the visible codepoints and bytes before each boundary
+    visible_before(*this, order, bound, vis, visb);
     // per segment between two boundaries that holds a visible item: its attribute set, compared
     // with the set of the segment with a visible item before it
     std::vector<SpanRec> sp;
@@ -1352,24 +1345,13 @@ int OpLog::apply_patches_bytes(const PatchRec* p, size_t n, const uint8_t* ins, 
     std::vector<uint32_t> order;
     err = document_order(order);
     if (!err.empty()) return CRDT_HIP_EBADLOG;
-    // ends[v]: UTF-8 bytes of the first v visible items, the only byte offsets a patch may name
-    std::vector<uint64_t> ends;
-    ends.reserve((size_t)nvis_ + 1);
-    ends.push_back(0);
-    for (uint32_t id : order)
-        if (!deleted[id - 1]) ends.push_back(ends.back() + utf8_len_cp(cp[id - 1]));
-    auto rank_of = [&](uint64_t b, uint64_t& v) {
-        const auto it = std::lower_bound(ends.begin(), ends.end(), b);
-        if (it == ends.end() || *it != b) return false;
-        v = (uint64_t)(it - ends.begin());
-        return true;
-    };
+    const std::vector<uint64_t> ends = byte_ends(*this, order);  // the only offsets a patch may name
     std::vector<PatchRec> q(n);
     int64_t shift = 0;  // codepoints inserted - deleted by the earlier patches
     for (size_t k = 0; k < n; ++k) {
         const BytePatch& e = plan.patch[k];
         uint64_t v0, v1;
-        if (!rank_of(e.old_pos_b, v0) || !rank_of(e.old_pos_b + e.del_b, v1)) {
+        if (!byte_rank(ends, e.old_pos_b, v0) || !byte_rank(ends, e.old_pos_b + e.del_b, v1)) {
             err = "patch boundary inside a codepoint";
             return CRDT_HIP_EINVAL;
         }
@@ -1529,6 +1511,68 @@ struct IdTable {
         }
     }
 };
+
+// What join and apply_diff share of "this <- this U foreign items, named by identity": the table of
+// the items held, the numbering and the bound of the new ones, the side-column check, and the two
+// ways the log changes.  The checks on an item both hold and the Fugue rules for a new one stay
+// with each caller: they differ in where a parent's identity comes from.
+struct Merge {
+    OpLog& log;
+    const uint32_t nd;  // items held before the call
+    IdTable dt;         // their identities
+    uint32_t nnew = 0, ntomb = 0;
+    explicit Merge(OpLog& l) : log(l), nd(l.size()), dt(nd) {}
+
+    int side_column(std::string& err) const {
+        if (log.fugue && log.side.size() != nd) {
+            err = "malformed op log (side column)";
+            return CRDT_HIP_EBADLOG;
+        }
+        return CRDT_HIP_OK;
+    }
+    // Fills dt, refusing two items of one identity with the caller's message; before_msg: also
+    // refuses, item by item, a parent that does not precede its item.
+    int build(const char* before_msg, const char* dup_msg, std::string& err) {
+        auto key = [&](uint32_t id) { return log.ident(id); };
+        for (uint32_t id = 1; id <= nd; ++id) {
+            if (before_msg && log.parent[id - 1] >= id) {
+                err = before_msg;
+                return CRDT_HIP_EBADLOG;
+            }
+            if (dt.insert(key(id), id, key)) {
+                err = dup_msg;
+                return CRDT_HIP_EBADLOG;
+            }
+        }
+        return CRDT_HIP_OK;
+    }
+    uint32_t held(uint64_t k) const {  // the id that holds identity k, or 0
+        return dt.find(k, [&](uint32_t id) { return log.ident(id); });
+    }
+    uint32_t fresh() { return nd + 1u + nnew++; }  // a new item's id: nd + 1 + its rank among them
+    int bound(std::string& err) const {
+        if ((uint64_t)nd + nnew >= 0x7FFFFFF0ull) {
+            err = "op log too large";
+            return CRDT_HIP_ERANGE;
+        }
+        return CRDT_HIP_OK;
+    }
+    void reserve(size_t dels) {  // dels: at least the entries the call adds to del_ops
+        if (!nnew) return;
+        log.reserve((size_t)nd + nnew, log.del_ops.size() + dels);
+        if (log.fugue) log.side.reserve((size_t)nd + nnew);
+    }
+    void tombstone(uint32_t d) {  // (an item this call appended counts as added, not tombstoned)
+        if (log.deleted[d - 1]) return;
+        log.del_ops.push_back(d);
+        log.mark_deleted(d);
+        ntomb += d <= nd;
+    }
+    void append(uint32_t par, uint32_t orr, uint64_t ident, bool del, uint32_t c, bool left) {
+        log.push_item(par, orr, (uint32_t)(ident >> 16), (uint16_t)ident, del, c, left);
+        if (del) log.del_ops.push_back(log.size());
+    }
+};
 }  // namespace
 
 int OpLog::join(uint32_t ns, const uint32_t* s_parent, const uint32_t* s_oright,
@@ -1543,12 +1587,9 @@ int OpLog::join(uint32_t ns, const uint32_t* s_parent, const uint32_t* s_oright,
         err = "join of a Fugue log with an RGA log: both sides must be of one kind";
         return CRDT_HIP_EINVAL;
     }
-    const uint32_t nd = size();
-    if (fugue) {  // the rules every path that takes a caller's Fugue view applies
-        if (side.size() != nd) {
-            err = "malformed op log (side column)";
-            return CRDT_HIP_EBADLOG;
-        }
+    Merge mg(*this);
+    if (int rc = mg.side_column(err)) return rc;
+    if (fugue)  // the rules every path that takes a caller's Fugue view applies
         for (uint32_t id = 1; id <= ns; ++id) {
             if (s_lamport[id - 1] == 0xFFFFFFFFu) {
                 err = "join: Fugue item with lamport 0xFFFFFFFF";
@@ -1559,25 +1600,15 @@ int OpLog::join(uint32_t ns, const uint32_t* s_parent, const uint32_t* s_oright,
                 return CRDT_HIP_EBADLOG;
             }
         }
-    }
-    auto dkey = [&](uint32_t id) { return ((uint64_t)lamport[id - 1] << 16) | agent[id - 1]; };
     auto skey = [&](uint32_t id) { return ((uint64_t)s_lamport[id - 1] << 16) | s_agent[id - 1]; };
     // ---- validate: nothing changes before every check has passed -------------------------------
-    IdTable dt(nd), st(ns);
-    for (uint32_t id = 1; id <= nd; ++id) {
-        if (parent[id - 1] >= id) {
-            err = "join: an item's parent does not precede it";
-            return CRDT_HIP_EBADLOG;
-        }
-        if (dt.insert(dkey(id), id, dkey)) {
-            err = "join: two items of the destination share an identity (lamport, agent)";
-            return CRDT_HIP_EBADLOG;
-        }
-    }
-    // src id -> id in this log (new items: nd + 1 + rank in src's slot order)
+    if (int rc = mg.build("join: an item's parent does not precede it",
+                          "join: two items of the destination share an identity (lamport, agent)", err))
+        return rc;
+    // src id -> id in this log (new items in src's slot order)
+    IdTable st(ns);
     std::vector<uint32_t> mp((size_t)ns + 1);
     mp[0] = 0;
-    uint32_t nnew = 0;
     for (uint32_t id = 1; id <= ns; ++id) {
         if (s_parent[id - 1] >= id) {
             err = "join: an item's parent does not precede it";
@@ -1588,18 +1619,15 @@ int OpLog::join(uint32_t ns, const uint32_t* s_parent, const uint32_t* s_oright,
             err = "join: two items of the source share an identity (lamport, agent)";
             return CRDT_HIP_EBADLOG;
         }
-        const uint32_t d = dt.find(k, dkey);
-        mp[id] = d ? d : nd + 1u + nnew++;
+        const uint32_t d = mg.held(k);
+        mp[id] = d ? d : mg.fresh();
     }
-    if ((uint64_t)nd + nnew >= 0x7FFFFFF0ull) {
-        err = "op log too large";
-        return CRDT_HIP_ERANGE;
-    }
-    uint32_t ntomb = 0, ndel_new = 0;
+    if (int rc = mg.bound(err)) return rc;
+    size_t ndels = 0;  // entries the join adds to del_ops: new tombstones of held and of new items
     for (uint32_t id = 1; id <= ns; ++id) {
         const uint32_t d = mp[id];
-        if (d > nd) {
-            ndel_new += s_deleted[id - 1] != 0;
+        if (d > mg.nd) {
+            ndels += s_deleted[id - 1] != 0;
             continue;
         }
         if ((cp[d - 1] ^ s_cp[id - 1]) & 0x1FFFFFu) {  // (codepoints: the device keeps 21 bits)
@@ -1614,30 +1642,24 @@ int OpLog::join(uint32_t ns, const uint32_t* s_parent, const uint32_t* s_oright,
             err = "join: an item both logs hold has another side in each";
             return CRDT_HIP_EBADLOG;
         }
-        ntomb += s_deleted[id - 1] && !deleted[d - 1];
+        ndels += s_deleted[id - 1] && !deleted[d - 1];
     }
     // ---- apply (src may be a view of this very log: then nothing is new and no column grows) ---
-    if (nnew) reserve((size_t)nd + nnew, del_ops.size() + ntomb + ndel_new);
-    if (nnew && fugue) side.reserve((size_t)nd + nnew);
+    mg.reserve(ndels);
     for (uint32_t id = 1; id <= ns; ++id) {
         const uint32_t d = mp[id];
-        if (d <= nd) {
-            if (s_deleted[id - 1] && !deleted[d - 1]) {
-                del_ops.push_back(d);
-                mark_deleted(d);
-            }
+        if (d <= mg.nd) {
+            if (s_deleted[id - 1]) mg.tombstone(d);
             continue;
         }
         // origin_right: an item id is translated like a parent; 0 and NIL (or anything beyond
         // src's ids) stay as they are
         const uint32_t o = s_oright ? s_oright[id - 1] : NIL;
-        const uint8_t del = s_deleted[id - 1] ? 1 : 0;
-        push_item(mp[s_parent[id - 1]], o && o <= ns ? mp[o] : o, s_lamport[id - 1],
-                  s_agent[id - 1], del, s_cp[id - 1], fugue && s_side[id - 1] ? 1 : 0);
-        if (del) del_ops.push_back(d);
+        mg.append(mp[s_parent[id - 1]], o && o <= ns ? mp[o] : o, skey(id), s_deleted[id - 1] != 0,
+                  s_cp[id - 1], fugue && s_side[id - 1]);
     }
-    if (added) *added = nnew;
-    if (tombstoned) *tombstoned = ntomb;
+    if (added) *added = mg.nnew;
+    if (tombstoned) *tombstoned = mg.ntomb;
     return CRDT_HIP_OK;
 }
 
@@ -1716,7 +1738,7 @@ int OpLog::encode_diff(const SvEntry* sv, size_t nsv, std::vector<uint8_t>& out,
         bound[sv[i].agent] = (uint64_t)sv[i].lamport + 1;
     }
     const uint32_t n = size();
-    auto key = [&](uint32_t k) { return ((uint64_t)lamport[k] << 16) | agent[k]; };
+    auto key = [&](uint32_t k) { return ident(k + 1); };  // of slot k, 0-based as the loops below
     auto covered = [&](uint32_t k) { return (uint64_t)lamport[k] < bound[agent[k]]; };
     std::vector<uint32_t> items, heads, counts;
     for (uint32_t k = 0; k < n; ++k) {
@@ -1756,32 +1778,31 @@ int OpLog::apply_diff(const uint8_t* buf, size_t len, uint32_t* added, uint32_t*
                       std::string& err) {
     if (added) *added = 0;
     if (tombstoned) *tombstoned = 0;
-    const uint32_t nd = size();
     DeltaFrame f;
-    int rc = delta_frame(buf, len, fugue, nd, f, err);
-    if (rc) return rc;
-    if (fugue && side.size() != nd) {
-        err = "malformed op log (side column)";
-        return CRDT_HIP_EBADLOG;
-    }
+    if (int rc = delta_frame(buf, len, fugue, size(), f, err)) return rc;
+    Merge mg(*this);
+    if (int rc = mg.side_column(err)) return rc;
     const uint32_t n = f.n;
     auto K = [&](uint32_t i) { return get64(buf + f.key + 8ull * i); };      // delta item i (0-based)
     auto PK = [&](uint32_t i) { return get64(buf + f.pkey + 8ull * i); };
     auto CP = [&](uint32_t i) { return get32(buf + f.cp + 4ull * i); };
-    auto dkey = [&](uint32_t id) { return ((uint64_t)lamport[id - 1] << 16) | agent[id - 1]; };
     auto ikey = [&](uint32_t e) { return K(e - 1); };  // (table entries are 1-based)
     const uint32_t reserved = ~(kDeltaCpMask | kDeltaTombBit | (fugue ? kDeltaSideBit : 0u));
     // ---- validate: nothing changes before every check has passed -------------------------------
-    IdTable dt(nd), it(n);
-    for (uint32_t id = 1; id <= nd; ++id)
-        if (dt.insert(dkey(id), id, dkey)) {
-            err = "delta: two items of the log share an identity (lamport, agent)";
-            return CRDT_HIP_EBADLOG;
-        }
-    // delta item -> id in this log (new items: nd + 1 + rank in the delta's order), and the
-    // translated parent of a new item
+    if (int rc = mg.build(nullptr, "delta: two items of the log share an identity (lamport, agent)", err))
+        return rc;
+    // delta item -> id in this log (new items in the delta's order), and the translated parent of
+    // a new item
+    IdTable it(n);
     std::vector<uint32_t> mp(n), tpar(n);
-    uint32_t nnew = 0;
+    // The id in this log of identity k: of an item the log holds, else of one of the delta's first
+    // `upto` items (0: neither).
+    auto where = [&](uint64_t k, uint32_t upto) -> uint32_t {
+        if (k >= kDeltaKeyEnd) return 0u;
+        if (const uint32_t d = mg.held(k)) return d;
+        const uint32_t e = it.find(k, ikey);
+        return e && e - 1 < upto ? mp[e - 1] : 0u;
+    };
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t k = K(i);
         const uint32_t c = CP(i);
@@ -1794,7 +1815,7 @@ int OpLog::apply_diff(const uint8_t* buf, size_t len, uint32_t* added, uint32_t*
             return CRDT_HIP_EBADLOG;
         }
         const uint64_t pk = PK(i);
-        const uint32_t d = dt.find(k, dkey);
+        const uint32_t d = mg.held(k);
         if (d) {  // the log holds the item
             mp[i] = d;
             const uint32_t p = parent[d - 1];
@@ -1802,7 +1823,7 @@ int OpLog::apply_diff(const uint8_t* buf, size_t len, uint32_t* added, uint32_t*
                 err = "delta: an item both hold has another codepoint in each";
                 return CRDT_HIP_EBADLOG;
             }
-            if ((p ? dkey(p) : kDeltaStart) != pk) {
+            if ((p ? ident(p) : kDeltaStart) != pk) {
                 err = "delta: an item both hold has another parent in each";
                 return CRDT_HIP_EBADLOG;
             }
@@ -1812,7 +1833,7 @@ int OpLog::apply_diff(const uint8_t* buf, size_t len, uint32_t* added, uint32_t*
             }
             continue;
         }
-        mp[i] = nd + 1u + nnew++;
+        mp[i] = mg.fresh();
         if (fugue) {
             if ((k >> 16) == 0xFFFFFFFFull) {
                 err = "delta: Fugue item with lamport 0xFFFFFFFF";
@@ -1827,21 +1848,14 @@ int OpLog::apply_diff(const uint8_t* buf, size_t len, uint32_t* added, uint32_t*
             tpar[i] = 0;
             continue;
         }
-        uint32_t p = pk < kDeltaKeyEnd ? dt.find(pk, dkey) : 0u;
-        if (!p && pk < kDeltaKeyEnd) {
-            const uint32_t e = it.find(pk, ikey);  // (an earlier item of the delta, new like this one)
-            if (e && e - 1 < i) p = mp[e - 1];
-        }
+        const uint32_t p = where(pk, i);  // (in the delta: an earlier item, new like this one)
         if (!p) {
             err = "delta: an item's parent is unknown or does not precede it";
             return CRDT_HIP_EBADLOG;
         }
         tpar[i] = p;
     }
-    if ((uint64_t)nd + nnew >= 0x7FFFFFF0ull) {
-        err = "op log too large";
-        return CRDT_HIP_ERANGE;
-    }
+    if (int rc = mg.bound(err)) return rc;
     // every identity of every range, after the items
     std::vector<uint32_t> rid;
     rid.reserve(f.range_items);
@@ -1850,14 +1864,7 @@ int OpLog::apply_diff(const uint8_t* buf, size_t len, uint32_t* added, uint32_t*
         const uint32_t cnt = get32(buf + f.rcount + 4ull * q);
         for (uint32_t j = 0; j < cnt; ++j) {
             const uint64_t k = k0 + ((uint64_t)j << 16);
-            uint32_t d = 0;
-            if (k0 < kDeltaKeyEnd && k < kDeltaKeyEnd) {
-                d = dt.find(k, dkey);
-                if (!d) {
-                    const uint32_t e = it.find(k, ikey);
-                    if (e) d = mp[e - 1];
-                }
-            }
+            const uint32_t d = k0 < kDeltaKeyEnd ? where(k, n) : 0u;
             if (!d) {
                 err = "delta: a tombstone range names an unknown item";
                 return CRDT_HIP_EBADLOG;
@@ -1866,30 +1873,19 @@ int OpLog::apply_diff(const uint8_t* buf, size_t len, uint32_t* added, uint32_t*
         }
     }
     // ---- apply ---------------------------------------------------------------------------------
-    if (nnew) reserve((size_t)nd + nnew, del_ops.size() + n + rid.size());
-    if (nnew && fugue) side.reserve((size_t)nd + nnew);
-    uint32_t ntomb = 0;
-    auto kill = [&](uint32_t d) {  // (an item appended by this delta counts as added, not tombstoned)
-        if (deleted[d - 1]) return;
-        del_ops.push_back(d);
-        mark_deleted(d);
-        ntomb += d <= nd;
-    };
+    mg.reserve((size_t)n + rid.size());
     for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t c = CP(i), d = mp[i];
-        if (d <= nd) {
-            if (c & kDeltaTombBit) kill(d);
+        const uint32_t c = CP(i);
+        if (mp[i] <= mg.nd) {
+            if (c & kDeltaTombBit) mg.tombstone(mp[i]);
             continue;
         }
-        const uint64_t k = K(i);
-        const uint8_t del = (c & kDeltaTombBit) ? 1 : 0;
-        push_item(tpar[i], NIL, (uint32_t)(k >> 16), (uint16_t)k, del, c & kDeltaCpMask,
-                  fugue && (c & kDeltaSideBit) ? 1 : 0);
-        if (del) del_ops.push_back(d);
+        mg.append(tpar[i], NIL, K(i), (c & kDeltaTombBit) != 0, c & kDeltaCpMask,
+                  fugue && (c & kDeltaSideBit));
     }
-    for (uint32_t d : rid) kill(d);
-    if (added) *added = nnew;
-    if (tombstoned) *tombstoned = ntomb;
+    for (uint32_t d : rid) mg.tombstone(d);
+    if (added) *added = mg.nnew;
+    if (tombstoned) *tombstoned = mg.ntomb;
     return CRDT_HIP_OK;
 }
 

@@ -215,6 +215,8 @@ public:
 
     OpLog();
     uint32_t size() const { return (uint32_t)parent.size(); }
+    // An item's identity, its name in every log that holds it (a Fugue item's side is no part of it).
+    uint64_t ident(uint32_t id) const { return ((uint64_t)lamport[id - 1] << 16) | agent[id - 1]; }
     uint64_t visible() const { return nvis_; }
     uint64_t visible_bytes() const;  // UTF-8 bytes of the visible items (walks the columns)
 

@@ -13,6 +13,21 @@ import patch_util as pu
 from crdt_hip import AFTER, BEFORE, DEAD, EDGE, LIVE, UNKNOWN
 
 EINVAL, ERANGE = -1, -2
+SHARED = 2 << 16    # the identity two slots of shared_identity_log() hold
+
+
+def shared_identity_log() -> crdt_hip.OpLog:
+    """A malformed host log "abcx": "abc" typed, then an update whose one item (id 4, parent 3,
+    origin_right NIL, lamport 2, agent 0, "x") takes the identity of slot 2."""
+    import struct
+    log = crdt_hip.OpLog()
+    log.insert(0, "abc")
+    #                 magic, version, first id, items, first del, dels | parent, oright, lamport, cp, agent
+    log.apply_update(struct.pack("<10IHH", 0x55445243, 1, 4, 1, 0, 0, 3, 0xFFFFFFFF, 2, ord("x"), 0, 0))
+    a = log.arrays()
+    assert log.text_at() == b"abcx" and a.n == 4
+    assert [(int(l) << 16) | int(g) for l, g in zip(a.lamport, a.agent)].count(SHARED) == 2
+    return log
 
 
 def utf8_len(cp: int) -> int:

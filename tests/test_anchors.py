@@ -176,3 +176,12 @@ def test_index_and_contents_are_untouched(oracle, kind):
     for l in (log, twin):
         l.insert(11, "zz")
     assert log.encode_diff([]) == twin.encode_diff([])
+
+
+def test_two_slots_of_one_identity_the_lower_wins():
+    """Of two slots of a malformed log that share an identity, an anchor names the lower one."""
+    log = au.shared_identity_log()
+    assert log.resolve_anchors([(au.SHARED, AFTER), (au.SHARED, BEFORE)]) == [(2, 2, LIVE), (1, 1, LIVE)]
+    log.remove(1, 2)
+    assert log.resolve_anchors([(au.SHARED, AFTER), (au.SHARED, BEFORE)]) == [(1, 1, DEAD)] * 2
+    assert log.text_at() == b"acx"

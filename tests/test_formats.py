@@ -10,6 +10,7 @@ import random
 import numpy as np
 import pytest
 
+import anchor_util as au
 import crdt_hip
 import format_util as fu
 import patch_util as pu
@@ -251,3 +252,13 @@ def test_host_adapter():
     off = a.unformat(0, 2, 1)
     assert off >> 16 > bold >> 16 and a.spans()[0][0] == (2, 1, {1: 1})
     assert a.unformat(0, 1, 2) >> 16 == (off >> 16) + 1   # the adapter's own clock moves on
+
+
+def test_two_slots_of_one_identity_the_lower_wins():
+    """Of two slots of a malformed log that share an identity, a format's anchors name the lower one."""
+    log = au.shared_identity_log()
+    on_b = fmt((au.SHARED, BEFORE), (au.SHARED, AFTER), 7, 9, op_of(1, 0))
+    assert log.spans([on_b]) == ([(1, 1, 1, 1, {7: 9})], 0)
+    log.remove(1, 2)
+    assert log.spans([on_b]) == ([], 0)
+    assert log.text_at() == b"acx"
