@@ -339,6 +339,7 @@ const Param kParams[] = {
     {"nsq_list", &Tunables::nsq_list, within<0, 2>, "nsq_list must be 0, 1 or 2"},
     {"static_jumps", &Tunables::static_jumps, within<0, 1>, "static_jumps must be 0 or 1"},
     {"dead_skip", &Tunables::dead_skip, within<0, 1>, "dead_skip must be 0 or 1"},
+    {"plain_tiles", &Tunables::plain_tiles, within<0, 1>, "plain_tiles must be 0 or 1"},
     {"doctree_k32", &Tunables::doctree_k32, within<0, 1>, "doctree_k32 must be 0 or 1"},
     {"glds_late", &Tunables::glds_late, nullptr, nullptr},
     {"plan_shrink", &Tunables::plan_shrink, nullptr, nullptr},

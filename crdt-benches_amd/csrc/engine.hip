@@ -189,6 +189,16 @@ struct L0Args {
     // character).  nsqb is then the resident nsq plane (DeviceLogs::nsq_mask), read-only in the
     // merge: k_classify_plane takes its nsq masks there and k_runs reads it as ever.
     const uint16_t* tomb;
+    // plain tiles (Engine::plain_wave: a plane wave whose batch keeps the plain-tile list,
+    // DeviceLogs::ptile; null otherwise, and the kernels are then instantiated without them): the
+    // wave's flag word per tile (bit 0 plain, bit 1 the jump bit of the slot before the tile),
+    // its list (busy tiles in tile order, then the plain ones with that jump bit in bit 31) and
+    // its busy count.  A plain tile holds one run head, its forced first slot, whose parent is
+    // the slot before it (head_word keeps the head whatever the tombstones say: no later word of
+    // the tile has a head, so its carry is set).
+    const uint32_t* ptf;
+    const uint32_t* ptl;
+    uint32_t nbusy;
 };
 
 constexpr uint32_t kTileBytes = kScanTile * 4;  // worst case: every slot a 4-byte character
@@ -638,6 +648,9 @@ __global__ __launch_bounds__(kBlock) void k_heads(L0Args a) {
 // not written: it is the resident nsq plane, which k_runs reads in its place.
 // Multi-byte text as in k_classify, for the visible characters only: a tombstoned multi-byte
 // character raises no escape.
+// PLAIN: the wave has a plain-tile list (L0Args::ptf), and a plain tile without a visible item
+// writes its tile pair alone (below); k_runs<.., PLAIN> reads nothing else of a plain tile.
+template <bool PLAIN>
 __global__ __launch_bounds__(kBlock) void k_classify_plane(L0Args a) {
     __shared__ uint32_t lds[kBlock / 64];
     // the threads' 16-bit nsq and visible masks, which the first wave reads back as 64 words
@@ -650,6 +663,7 @@ __global__ __launch_bounds__(kBlock) void k_classify_plane(L0Args a) {
     const bool live = gs < a.nslots;
     const uint32_t nlo = a.nsq_pre[t0 >> 6];
     const uint32_t nhi = a.nsq_pre[min(t0 + kScanTile, a.nslots) >> 6];
+    const uint32_t pfl = PLAIN ? a.ptf[tile] : 0u;
     uint32_t tb = 0xFFFFu, nq = 0;
     if (live) {
         tb = a.tomb[gs >> 4];
@@ -670,6 +684,22 @@ __global__ __launch_bounds__(kBlock) void k_classify_plane(L0Args a) {
         const uint4* cv = reinterpret_cast<const uint4*>(a.in_cp + 3ull * gs);  // 48 B
 #pragma unroll
         for (int q = 0; q < 3; ++q) cq[q] = cv[q];
+    }
+    // A plain tile (PLAIN: L0Args::ptf) without a visible item has one head, its first slot, and
+    // weighs nothing: k_runs takes neither head records, visible bits nor escape words of a plain
+    // tile (runs_plain), and nobody's parent lies in one, so the tile's pair is all it writes.
+    // Every wave reads the tile's 64 tombstone words (lane = word; the 512 bytes its own masks
+    // lie in) and decides alone: no barrier.  The flag is loaded with the planes and tested once
+    // they are here, so a busy tile waits for nothing more.  A batch with a bad parent (the
+    // sticky flag k_clear put into the error word before this launch) keeps the head records:
+    // k_runs looks such a parent up wherever it points.
+    if (PLAIN && (pfl & 1u) && !(a.ctl[C_ERR] & 1u)) {
+        const uint64_t tw64 =
+            reinterpret_cast<const uint64_t*>(a.tomb)[tile * (kScanTile / 64) + (threadIdx.x & 63u)];
+        if (__ballot(tw64 != ~0ull) == 0ull) {
+            if (threadIdx.x == 0) a.tile_hw[tile] = make_uint2(1u, 0u);
+            return;
+        }
     }
     // the planes were built from the document table (k_nsq_count, k_raw_encode): the tombstone
     // plane marks every slot that is no item and the nsq plane holds items only, so the masks
@@ -870,8 +900,62 @@ __global__ __launch_bounds__(kBlock) void k_tiles_one(L0Args a) {
 constexpr uint32_t kRunsWin = 1024;
 __device__ __forceinline__ uint32_t mpop(uint32_t x) { return (uint32_t)__popc(x); }
 __device__ __forceinline__ uint32_t mpop(uint64_t x) { return (uint32_t)__popcll(x); }
-template <bool FUGUE, int SL>
+// The plain tiles of a wave (L0Args::ptl), one per thread: block pb of the blocks behind the busy
+// tiles' takes plain tiles [pb NT, pb NT + NT) of the list.  A plain tile's one run starts at its
+// first slot with the tile's weight prefix, and its parent is the run before it (the run of the
+// slot before the tile, which is always kept: head_word's carry at a tile's last word).  Its key
+// is compared with a sibling's only if that slot has another child, a jump bit (the list's bit
+// 31): an only child's key stays 0 and is not gathered.  The tile's weight is the next prefix
+// less its own (the wave totals for the last tile); a plain tile with visible text is rare, so
+// where k_runs copies the text the block then moves such tiles' bytes one tile at a time.
+// lds: 3 NT words.
+template <int NT>
+__device__ __forceinline__ void runs_plain(const L0Args& a, uint32_t pb, uint32_t nbusy, uint32_t* lds) {
+    const uint32_t np = a.ntiles - nbusy;
+    if (pb * NT >= np) return;
+    const uint32_t i = pb * NT + threadIdx.x;
+    uint32_t tile = 0, D = 0, tw = 0;
+    if (i < np) {
+        const uint32_t ent = a.ptl[nbusy + i];
+        tile = ent & 0x7FFFFFFFu;
+        const uint2 pre = a.tile_hw[tile];
+        const bool last = tile + 1u == a.ntiles;
+        const uint2 nx = last ? make_uint2(a.ctl[C_RTOTAL], a.ctl[C_WTOTAL]) : a.tile_hw[tile + 1u];
+        const uint32_t g = tile * kScanTile, rho = pre.x;
+        if (nx.x != pre.x) {
+            a.r_head[rho] = g;
+            a.r_pstart[rho] = pre.y;
+            if (rho < a.cap_rows) {  // (beyond: the wave outgrew its plan, C_REPLAN follows)
+                a.r_parent[rho] = rho - 1u;
+                a.r_key[rho] = (ent >> 31) ? a.in_key[g] : 0ull;
+            }
+        }
+        if (last) a.r_pstart[nx.x] = nx.y;
+        D = pre.y;
+        tw = nx.y - pre.y;
+        if (a.mode == 0 && tw && (uint64_t)D + tw > a.sbytes_cap) {  // more text than the host bound
+            atomicOr(&a.ctl[C_ERR], 4u);
+            tw = 0;
+        }
+    }
+    if (!(a.mode == 0 && a.copy_text)) return;
+    if (__syncthreads_or(tw != 0u) == 0) return;
+    lds[3 * threadIdx.x] = tile;
+    lds[3 * threadIdx.x + 1] = D;
+    lds[3 * threadIdx.x + 2] = tw;
+    __syncthreads();
+    for (uint32_t k = 0; k < NT; ++k) {
+        const uint32_t n = lds[3 * k + 2];
+        if (!n) continue;
+        const uint8_t* src = a.stile + (uint64_t)lds[3 * k] * kTileBytes;
+        uint8_t* dst = a.sbytes + lds[3 * k + 1];
+        for (uint32_t b = threadIdx.x; b < n; b += NT) dst[b] = src[b];
+    }
+}
+
+template <bool FUGUE, int SL, bool PLAIN = false>
 __global__ __launch_bounds__(kScanTile / SL) __attribute__((amdgpu_waves_per_eu(8))) void k_runs(L0Args a) {
+    static_assert(!(FUGUE && PLAIN), "plain tiles: RGA waves");
     static_assert(SL == 16 || SL == 32 || SL == 64, "slots per thread");
     using MT = typename std::conditional<SL == 64, uint64_t, uint32_t>::type;  // a thread's slot masks
     constexpr int NT = kScanTile / SL;  // threads per tile
@@ -887,7 +971,19 @@ __global__ __launch_bounds__(kScanTile / SL) __attribute__((amdgpu_waves_per_eu(
     __shared__ uint16_t lnpf[NT];      // non-seq items of the tile before every thread
     __shared__ uint16_t ldp[FUGUE ? NT : 1];  // Fugue: two-row heads before every thread
     __shared__ MT ldm[FUGUE ? NT : 1];        //   and every thread's two-row head bits
-    const uint32_t tile = xcd_block(blockIdx.x, gridDim.x, a.xcd);
+    // PLAIN (L0Args::ptl): the first nbusy blocks take the busy tiles through the list (each XCD
+    // still walks one contiguous range of them) and the blocks behind them the plain tiles
+    uint32_t tile;
+    if constexpr (PLAIN) {
+        if (blockIdx.x >= a.nbusy) {
+            static_assert(3 * NT <= kWin + 1, "runs_plain's words fit the record window");
+            runs_plain<NT>(a, blockIdx.x - a.nbusy, a.nbusy, rec);
+            return;
+        }
+        tile = a.ptl[xcd_block(blockIdx.x, a.nbusy, a.xcd)];
+    } else {
+        tile = xcd_block(blockIdx.x, gridDim.x, a.xcd);
+    }
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     const uint32_t gs = tile * kScanTile + threadIdx.x * SL;
     MT hm = 0, nsq = 0, dm = 0;
@@ -4069,6 +4165,63 @@ __global__ __launch_bounds__(kBlock) void k_nsq_scatter(L0Args a, const uint32_t
     }
 }
 
+// ---- the plain-tile list of a resident batch (DeviceLogs::ptile; Engine::plain_list) -----------
+// k_plain_flag, after k_nsq_scatter has set every jump bit of the wave: one wave per tile, lane =
+// 64-slot word.  The tile is plain when every word lies inside the wave, all 64 slots of it are
+// items of its document (so the tile holds no document start and no padding; a second document
+// would start inside it), and its nsq mask word and its jump word are 0.  Bit 1 of the flag: the
+// jump bit of the slot before the tile (a plain tile is never a wave's first: that one holds a
+// document start).
+__global__ __launch_bounds__(kBlock) void k_plain_flag(L0Args a, const uint64_t* __restrict__ mask,
+                                                      uint32_t* __restrict__ flag) {
+    const uint32_t tile = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (tile >= a.ntiles) return;
+    const uint32_t wi = tile * (kScanTile / 64) + lane, gs = wi * 64u;
+    bool ok = (uint64_t)gs + 64u <= a.nslots;
+    if (ok) {
+        const uint2 doc = a.docs[a.chunk_doc[gs >> a.log2m]];
+        const uint32_t l0 = gs - doc.x;  // (item index of the word's first slot; 0: the start)
+        ok = l0 > 0u && (uint64_t)l0 + 63u <= doc.y && mask[wi] == 0ull &&
+             *reinterpret_cast<const uint64_t*>(a.jbits + 2u * wi) == 0ull;
+    }
+    const bool plain = __ballot(!ok) == 0ull;
+    if (lane == 0u) flag[tile] = plain ? 1u | (((a.jbits[2u * wi - 1u] >> 31) & 1u) << 1) : 0u;
+}
+// k_plain_list, one workgroup per wave: the busy tiles in tile order, then the plain ones (bit 31:
+// the flag's bit 1), and the busy count.
+__global__ __launch_bounds__(1024) void k_plain_list(uint32_t ntiles, const uint32_t* __restrict__ flag,
+                                                     uint32_t* __restrict__ list,
+                                                     uint32_t* __restrict__ nbusy) {
+    __shared__ uint32_t lds[16];
+    constexpr uint32_t kPer = 16;  // consecutive tiles per thread and round
+    uint32_t c = 0, nb;
+    for (uint32_t t = threadIdx.x; t < ntiles; t += 1024u) c += (flag[t] & 1u) ^ 1u;
+    (void)block_excl_scan<16>(c, lds, nb);
+    if (threadIdx.x == 0) *nbusy = nb;
+    uint32_t carry = 0;
+    for (uint32_t t0 = 0; t0 < ntiles; t0 += 1024u * kPer) {
+        const uint32_t t1 = t0 + threadIdx.x * kPer;
+        uint32_t f[kPer], busy = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kPer; ++k) {
+            f[k] = t1 + k < ntiles ? flag[t1 + k] : 1u;
+            busy += (f[k] & 1u) ^ 1u;
+        }
+        uint32_t tot;
+        uint32_t bi = carry + block_excl_scan<16>(busy, lds, tot);  // busy tiles before t1
+        carry += tot;
+#pragma unroll
+        for (uint32_t k = 0; k < kPer; ++k)
+            if (t1 + k < ntiles) {
+                const uint32_t t = t1 + k;
+                if (f[k] & 1u)
+                    list[nb + (t - bi)] = t | ((f[k] >> 1) << 31);  // (t - bi: plain tiles before t)
+                else
+                    list[bi++] = t;
+            }
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void k_replicate(
     const uint32_t* __restrict__ bp, const uint64_t* __restrict__ bk,
     const uint8_t* __restrict__ bc,
@@ -4137,11 +4290,13 @@ inline uint32_t ceil_log2(uint64_t x) {
 void DeviceLogs::release() {
     dfree(parent); dfree(key); dfree(cp);
     dfree(nsq_par); dfree(nsq_pre); dfree(nsq_key); dfree(nsq_sums); dfree(nsq_mask); dfree(tomb); dfree(jump);
+    dfree(ptile);
     nsq_items = 0;
     nsq_ok = false;
     jump_ok = false;
     tomb_ok = false;
-    nsq_cap = nsq_pre_cap = nsq_sums_cap = jump_cap = 0;
+    ptile_ok = false;
+    nsq_cap = nsq_pre_cap = nsq_sums_cap = jump_cap = ptile_cap = 0;
     dfree(docs_rel); dfree(doc_rank); dfree(chunk_doc);
     dfree(raw_lam); dfree(raw_agent); dfree(raw_del); dfree(raw_cp);
     raw = false;
@@ -4236,6 +4391,7 @@ int Engine::plan(DeviceLogs& L, const std::vector<DocInfo>& docs,
     L.nsq_ok = false;
     L.jump_ok = false;
     L.tomb_ok = false;
+    L.ptile_ok = false;
     L.nsq_items = 0;
     L.log2m = kDocAlignLog2;
     L.docs = docs;
@@ -4731,6 +4887,12 @@ L0Args Engine::wave_args<L0Args>(const DeviceLogs& L, const Wave& w, bool ord) c
     a0.jbits = a0.sjump ? L.jump + DeviceLogs::kJumpHead + (w.slot0 >> 5) : jbits_;
     a0.tomb = plane_wave(L, w, ord) ? reinterpret_cast<const uint16_t*>(L.tomb + (w.slot0 >> 6)) : nullptr;
     a0.nsqb = a0.tomb ? reinterpret_cast<uint16_t*>(L.nsq_mask + (w.slot0 >> 6)) : nsqb_;
+    if (plain_wave(L, w, ord) && w.nbusy != Wave::kNoBusy) {
+        const uint64_t wi = (uint64_t)(&w - L.waves.data());
+        a0.ptf = L.ptile + L.ptile_base(wi);
+        a0.ptl = a0.ptf + L.ptile_tiles();
+        a0.nbusy = w.nbusy;
+    }
     a0.wnib = wnib_;
     a0.visb = visb_;
     a0.escm = escm_;
@@ -4794,7 +4956,20 @@ TreeArgs Engine::wave_args<TreeArgs>(const DeviceLogs& L, const Wave& w, bool or
 }
 
 // k_runs with 16, 32 or 64 slots per thread (Engine::runs_slots)
+// (with a plain-tile list: a block per busy tile, then the blocks of runs_plain, a thread per
+// plain tile)
 void launch_k_runs(const L0Args& a0, uint32_t ntiles, hipStream_t s, uint32_t slots) {
+    if (a0.ptl) {
+        const uint32_t nt = (uint32_t)kScanTile / slots;
+        const uint32_t grid = a0.nbusy + (ntiles - a0.nbusy + nt - 1) / nt;
+        if (slots == 64)
+            k_runs<false, 64, true><<<grid, kScanTile / 64, 0, s>>>(a0);
+        else if (slots == 32)
+            k_runs<false, 32, true><<<grid, kScanTile / 32, 0, s>>>(a0);
+        else
+            k_runs<false, 16, true><<<grid, kScanTile / 16, 0, s>>>(a0);
+        return;
+    }
     if (a0.fugue) {
         if (slots == 64)
             k_runs<true, 64><<<ntiles, kScanTile / 64, 0, s>>>(a0);
@@ -4828,8 +5003,10 @@ int Engine::launch_level0(DeviceLogs& L, const Wave& w, bool ord, bool copy_text
     k_clear<<<std::max(1u, std::min<uint32_t>(grid_for(nq), 2048u)), 256, 0, s>>>(
         ctl_, reinterpret_cast<uint4*>(jbits_), nq, a0.sjump ? L.jump : nullptr);
     MARK(-1);
-    if (a0.tomb)
-        k_classify_plane<<<ntiles, kBlock, 0, s>>>(a0);
+    if (a0.ptf)
+        k_classify_plane<true><<<ntiles, kBlock, 0, s>>>(a0);
+    else if (a0.tomb)
+        k_classify_plane<false><<<ntiles, kBlock, 0, s>>>(a0);
     else
         k_classify<<<ntiles, kBlock, 0, s>>>(a0);
     MARK(S_CLASSIFY);
@@ -5754,6 +5931,7 @@ int Engine::build_nsq(DeviceLogs& L) {
         w.nsq_items = b[1] - b[0];
     }
     HIPCHK(hipStreamSynchronize(stream), "nsq list");
+    if (int rc = plain_list(L)) return rc;
     L.nsq_items = total;
     L.nsq_ok = true;
     set_contraction(L);
@@ -5791,6 +5969,15 @@ int Engine::nsq_reserve_prefix(DeviceLogs& L) {
         L.jump_ok = false;
         HIPCHK(dalloc(&L.jump, jw), "hipMalloc jump bits");
         L.jump_cap = jw;
+        gen_++;
+    }
+    // the plain-tile list beside them
+    if (plain_tiles && L.jump && L.ptile_words() > L.ptile_cap) {
+        dfree(L.ptile);
+        L.ptile_cap = 0;
+        L.ptile_ok = false;
+        HIPCHK(dalloc(&L.ptile, L.ptile_words()), "hipMalloc plain tiles");
+        L.ptile_cap = L.ptile_words();
         gen_++;
     }
     return CRDT_HIP_OK;
@@ -5974,6 +6161,33 @@ void Engine::nsq_scatter(DeviceLogs& L) {
             sj ? L.jump + DeviceLogs::kJumpHead + (w.slot0 >> 5) : nullptr, L.jump);
     }
     L.jump_ok = sj;
+    // (the plain-tile list was made from the bits before these: plain_list builds it again)
+    L.ptile_ok = false;
+    for (Wave& w : L.waves) w.nbusy = Wave::kNoBusy;
+}
+
+// The plain-tile list of L (DeviceLogs::ptile) from its complete jump bits and nsq masks, wave by
+// wave, and every wave's busy count for k_runs' grid.  Part of the one-time encoding of a
+// resident batch (build_nsq): lists rebuilt inside a merge (replicas, raw SoA mode) go without,
+// and their waves take a workgroup per tile as before.
+int Engine::plain_list(DeviceLogs& L) {
+    if (!(plain_tiles && L.jump_ok && L.ptile && L.ptile_cap >= L.ptile_words())) return CRDT_HIP_OK;
+    for (size_t wi = 0; wi < L.waves.size(); ++wi) {
+        const Wave& w = L.waves[wi];
+        L0Args a0 = wave_args<L0Args>(L, w, false);
+        a0.jbits = L.jump + DeviceLogs::kJumpHead + (w.slot0 >> 5);
+        uint32_t* flag = L.ptile + L.ptile_base(wi);
+        k_plain_flag<<<(a0.ntiles + kBlock / 64 - 1) / (kBlock / 64), kBlock, 0, stream>>>(
+            a0, L.nsq_mask + (w.slot0 >> 6), flag);
+        k_plain_list<<<1, 1024, 0, stream>>>(a0.ntiles, flag, flag + L.ptile_tiles(), L.ptile + wi);
+    }
+    HIPCHK(hipGetLastError(), "plain tile list launch");
+    for (size_t wi = 0; wi < L.waves.size(); ++wi)
+        HIPCHK(hipMemcpyAsync(&L.waves[wi].nbusy, L.ptile + wi, 4, hipMemcpyDeviceToHost, stream),
+               "plain tile counts");
+    HIPCHK(hipStreamSynchronize(stream), "plain tile list");
+    L.ptile_ok = true;
+    return CRDT_HIP_OK;
 }
 
 int Engine::nsq_reserve(DeviceLogs& L) {

@@ -47,6 +47,11 @@ struct Wave {
     // encoding (Engine::build_nsq, Engine::upload) or forced by Engine::contraction
     bool nocon = false;
     uint64_t nsq_items = 0;  // items of the wave without the previous-slot flag (if known)
+    // busy tiles of the wave in the batch's plain-tile list (DeviceLogs::ptile), read back when
+    // it is built (Engine::plain_list): k_runs' grid is the busy tiles plus the few blocks of the
+    // plain ones.  kNoBusy: the batch has no list, and every tile is busy.
+    static constexpr uint32_t kNoBusy = 0xFFFFFFFFu;
+    uint32_t nbusy = kNoBusy;
 };
 
 // Stage timing of one wave: an event at its start and after every stage that ran.
@@ -156,6 +161,25 @@ struct DeviceLogs {
     uint32_t* jump = nullptr;
     uint64_t jump_cap = 0;   // words allocated
     bool jump_ok = false;    // the bits match the list (set with it; plan() clears it)
+    // The plain-tile list (Engine::plain_tiles), built from the jump bits and the nsq plane when
+    // a resident batch is encoded (Engine::plain_list, from build_nsq) and valid with them
+    // (ptile_ok: plan() clears it, and so does every rebuild of the bits inside a merge, which
+    // replicas and raw SoA batches do: their waves go without the list).  A 4096-slot tile of a wave is plain
+    // when every slot of it is an item of one document with the previous-slot flag and without a
+    // jump bit: the inside of one typed run, which holds no run head but the tile's forced first
+    // one, no listed item and nobody's parent.  A function of the parent column alone; nothing of
+    // it derives from a tombstone.  One allocation of u32: a busy-tile count per wave
+    // (ptile_head() words), then per tile of every wave (wave wi from ptile_base(wi)) a flag word
+    // (bit 0 plain, bit 1 the jump bit of the slot before the tile) and, after all flags, the
+    // wave's list: its busy tiles in tile order, then its plain tiles (bit 31: that jump bit).
+    uint32_t* ptile = nullptr;
+    uint64_t ptile_cap = 0;   // words allocated
+    bool ptile_ok = false;
+    uint64_t ptile_head() const { return (waves.size() + 63) & ~63ull; }  // the counts
+    uint64_t ptile_tiles() const { return (total_slots >> 12) + waves.size() + 1; }
+    uint64_t ptile_words() const { return ptile_head() + 2 * ptile_tiles(); }
+    // wave wi's first tile in the flags (and, ptile_tiles() further, in the lists)
+    uint64_t ptile_base(uint64_t wi) const { return ptile_head() + (waves[wi].slot0 >> 12) + wi; }
     // Raw SoA mode (Engine::raw_keep, the companion line that prices the input encoding): the
     // reference-shaped columns beside the parent column, lamport u32, agent u16, deleted u8 and
     // codepoint u32 per slot; every merge first derives the key, the codepoint word with its
@@ -214,6 +238,10 @@ struct Tunables {
     // visible item; nsqb is not written, k_runs reads the resident nsq plane.  0: k_classify
     // reads the codepoint word of every slot.
     uint64_t dead_skip = 1;
+    // 1: waves on the plane path take the batch's plain-tile list (DeviceLogs::ptile): k_runs
+    // gives a workgroup to every busy tile and a thread to every plain one, and k_classify_plane
+    // leaves a plain tile without a visible item after its first loads.  0: every tile is busy.
+    uint64_t plain_tiles = 1;
     // run contraction of RGA waves: 0 = by the wave's input (no contraction when at least
     // kNoconShare of its items lack the previous-slot flag), 1 = always, 2 = never
     uint64_t contraction = 0;
@@ -259,6 +287,9 @@ public:
     }
     bool plane_wave(const DeviceLogs& L, const Wave& w, bool ord) const {
         return dead_skip && !ord && static_wave(L, w) && L.tomb && L.tomb_ok;
+    }
+    bool plain_wave(const DeviceLogs& L, const Wave& w, bool ord) const {
+        return plain_tiles && plane_wave(L, w, ord) && L.ptile && L.ptile_ok;
     }
     static constexpr uint64_t kNsqReplicaSlots = 1ull << 22;
     std::string err;
@@ -327,6 +358,7 @@ public:
     void nsq_count_scan(DeviceLogs& L);
     void nsq_scan(DeviceLogs& L);
     void nsq_scatter(DeviceLogs& L);
+    int plain_list(DeviceLogs& L);
     // Wave::nocon of every wave of L from its nsq_items and the contraction parameter.
     void set_contraction(DeviceLogs& L) const;
     // The compact nsq list of logs that change (replicas): room for every slot (nsq_reserve,

@@ -190,7 +190,10 @@ const char* crdt_hip_last_error(const crdt_hip_ctx* ctx);
  * and previous-slot flags as bit planes of their own, one bit per slot each, built with the list,
  * and text merges fetch the codepoints only of 16-slot groups that hold a visible character;
  * every merge still reads every slot's tombstone; 0 = the flags are read from the codepoint word
- * of every slot), "contraction" (run contraction of RGA waves, decided
+ * of every slot), "plain_tiles" (default 1: resident batches on that path also keep a list of
+ * their plain 4096-slot tiles, the inside of one typed run, a function of the parent column alone;
+ * such a tile takes a thread of k_runs instead of a workgroup; 0 = a workgroup per tile),
+ * "contraction" (run contraction of RGA waves, decided
  * when a batch is built or logs are uploaded: 0 = by the input (default: no contraction when at
  * least 3/4 of a wave's items lack the previous-slot flag), 1 = always, 2 = never; replica
  * merges, which count no flags, contract under 0 and 1 and never under 2), "l1_group"
