@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "crdt_hip.h"
+#include "crdt_hip_lines.h"
 #include "engine.hpp"
 #include "oplog.hpp"
 #include "replica.hpp"
@@ -44,6 +45,7 @@ struct crdt_hip_ctx {
     crdt::AnchorStats last_anchor;  // what the last device anchors_at / anchors_resolve observed
     crdt::FormatStats last_format;  // what the last device spans observed
     crdt::TextStats last_text;      // what the last device text_at observed
+    crdt::LineStats last_line;      // what the last device line_starts / lines_of observed
 };
 namespace {
 // Names the owner of a mark: every log and replica handle gets its own, a clone included.
@@ -1099,6 +1101,50 @@ int crdt_hip_text_stats(const crdt_hip_ctx* ctx, uint64_t* ranks, uint64_t* tile
     if (!ctx) return null_ctx();
     const crdt::TextStats& s = ctx->last_text;
     put(ranks, s.ranks, tiles_written, s.tiles_written, bytes, s.bytes, device_ns, s.device_ns);
+    return 0;
+}
+// ---- the line index (crdt_hip_lines.h): line starts, and line / column of positions -----------------
+static_assert(sizeof(crdt_hip_line_pos) == sizeof(crdt::LinePos) && sizeof(crdt_hip_line_pos) == 40 &&
+                  sizeof(crdt_hip_line_info) == sizeof(crdt::LineInfo) && sizeof(crdt_hip_line_info) == 24,
+              "line layouts");
+int crdt_hip_oplog_line_starts(crdt_hip_oplog* log, const crdt_hip_mark* m, const uint64_t* lines,
+                               size_t n, crdt_hip_line_pos* out, crdt_hip_line_info* info) {
+    if (int rc = check_log_mark(log, m, true, true)) return rc;
+    return host([&](std::string& e) {
+        return log->log.line_starts(m ? &m->host : nullptr, lines, n, reinterpret_cast<crdt::LinePos*>(out),
+                                    reinterpret_cast<crdt::LineInfo*>(info), e);
+    });
+}
+int crdt_hip_oplog_lines_of(crdt_hip_oplog* log, const crdt_hip_mark* m, const uint64_t* pos, size_t n,
+                            uint32_t flags, crdt_hip_line_pos* out, crdt_hip_line_info* info) {
+    if (int rc = check_log_mark(log, m, true, true)) return rc;
+    return host([&](std::string& e) {
+        return log->log.lines_of(m ? &m->host : nullptr, pos, n, flags, reinterpret_cast<crdt::LinePos*>(out),
+                                 reinterpret_cast<crdt::LineInfo*>(info), e);
+    });
+}
+int crdt_hip_replica_line_starts(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_mark* m,
+                                 const uint64_t* lines, size_t n, crdt_hip_line_pos* out,
+                                 crdt_hip_line_info* info) {
+    return device(ctx, check_replica_mark(ctx, r, m, true, true), [&] {
+        return crdt::replica_lines(ctx->eng, r->r, m ? &m->dev : nullptr, false, lines, n, 0,
+                                   reinterpret_cast<crdt::LinePos*>(out),
+                                   reinterpret_cast<crdt::LineInfo*>(info), &ctx->last_line);
+    });
+}
+int crdt_hip_replica_lines_of(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_mark* m,
+                              const uint64_t* pos, size_t n, uint32_t flags, crdt_hip_line_pos* out,
+                              crdt_hip_line_info* info) {
+    return device(ctx, check_replica_mark(ctx, r, m, true, true), [&] {
+        return crdt::replica_lines(ctx->eng, r->r, m ? &m->dev : nullptr, true, pos, n, flags,
+                                   reinterpret_cast<crdt::LinePos*>(out),
+                                   reinterpret_cast<crdt::LineInfo*>(info), &ctx->last_line);
+    });
+}
+int crdt_hip_line_stats(const crdt_hip_ctx* ctx, uint64_t* queries, uint64_t* ranks, uint64_t* device_ns) {
+    if (!ctx) return null_ctx();
+    const crdt::LineStats& s = ctx->last_line;
+    put(queries, s.queries, ranks, s.ranks, device_ns, s.device_ns);
     return 0;
 }
 // ---- anchors: cursor and selection positions that survive sync --------------------------------------

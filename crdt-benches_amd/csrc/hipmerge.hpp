@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "crdt_hip.h"
+#include "crdt_hip_lines.h"
 
 namespace hipmerge {
 
@@ -93,6 +94,34 @@ std::string text_get(Call&& call, crdt_hip_ctx* ctx, size_t start, size_t end, b
     check(rc, ctx, "text_at");
     out.resize(n);
     return out;
+}
+
+// The line index (crdt_hip_lines.h): where lines start, and the line and column of positions.
+using LinePos = crdt_hip_line_pos;
+// call(queries, n, out, info) -> the n records.  `beyond`: where a query beyond the version
+// (CRDT_HIP_ERANGE) is reported instead of being fatal (text_lines clips then).
+template <class Call>
+std::vector<LinePos> lines_get(Call&& call, crdt_hip_ctx* ctx, const std::vector<uint64_t>& q,
+                               crdt_hip_line_info* info = nullptr, bool* beyond = nullptr) {
+    std::vector<LinePos> out(q.size());
+    const int rc = call(q.data(), q.size(), out.data(), info);
+    if (beyond) *beyond = rc == CRDT_HIP_ERANGE;
+    if (!(beyond && *beyond)) check(rc, ctx, "lines");
+    return out;
+}
+// Lines first .. first + count of a version as UTF-8, line breaks included, clipped to the version:
+// starts(lines, info, beyond) is line_starts, window(start_bytes, end_bytes) the byte window.
+template <class Starts, class Window>
+std::string text_lines_get(Starts&& starts, Window&& window, size_t first, size_t count) {
+    bool beyond = false;
+    std::vector<LinePos> s = starts({(uint64_t)first, (uint64_t)first + count}, nullptr, &beyond);
+    if (beyond) {
+        crdt_hip_line_info info{};
+        starts({}, &info, nullptr);
+        s = starts({std::min<uint64_t>(first, info.lines), std::min<uint64_t>((uint64_t)first + count, info.lines)},
+                   nullptr, nullptr);
+    }
+    return window((size_t)s[0].start_bytes, (size_t)s[1].start_bytes);
 }
 
 // A cursor, a selection end: a place in the text that survives every edit and sync and means the
@@ -295,6 +324,26 @@ public:
     std::string text_at(const Mark& m, size_t start = 0, size_t end = std::string::npos) const {
         return text_window(m.get(), start, end);
     }
+    // The line index (crdt_hip_lines.h) of the document now (m null) or as of a mark: where the
+    // lines `lines` (0..L + 1, the last one the end) start, the line and column of gap positions,
+    // and lines first .. first + count as text, clipped to the version (a viewport by lines).
+    std::vector<LinePos> line_starts(const std::vector<uint64_t>& lines, const crdt_hip_mark* m = nullptr) const {
+        return line_starts_of(lines, m, nullptr, nullptr);
+    }
+    std::vector<LinePos> lines_of(const std::vector<uint64_t>& pos, const crdt_hip_mark* m = nullptr) const {
+        return lines_get(
+            [&](const uint64_t* q, size_t n, LinePos* out, crdt_hip_line_info* info) {
+                return crdt_hip_oplog_lines_of(log_.get(), m, q, n, 0, out, info);
+            },
+            nullptr, pos);
+    }
+    std::string text_lines(size_t first, size_t count, const crdt_hip_mark* m = nullptr) const {
+        return text_lines_get(
+            [&](const std::vector<uint64_t>& q, crdt_hip_line_info* info, bool* beyond) {
+                return line_starts_of(q, m, info, beyond);
+            },
+            [&](size_t a, size_t b) { return text_window(m, a, b, true); }, first, count);
+    }
     // The anchor of gap `pos` (bias: CRDT_HIP_ANCHOR_AFTER sticks to the item before the gap,
     // BEFORE to the one after it), and where anchors made here or on any peer lie now.
     Anchor anchor_at(size_t pos, uint32_t bias = CRDT_HIP_ANCHOR_AFTER) const {
@@ -346,13 +395,21 @@ private:
                             anchor_at(end, expand & EXPAND_END ? CRDT_HIP_ANCHOR_BEFORE : CRDT_HIP_ANCHOR_AFTER),
                             key, value, flags, sv);
     }
-    std::string text_window(const crdt_hip_mark* m, size_t start, size_t end) const {
+    std::string text_window(const crdt_hip_mark* m, size_t start, size_t end, bool bytes = false) const {
         return text_get(
             [&](uint64_t s, uint64_t e, uint32_t flags, uint8_t* out, size_t cap, size_t* n,
                 crdt_hip_text_info* info) {
                 return crdt_hip_oplog_text_at(log_.get(), m, s, e, flags, out, cap, n, info);
             },
-            nullptr, start, end, false, 1 << 12);
+            nullptr, start, end, bytes, 1 << 12);
+    }
+    std::vector<LinePos> line_starts_of(const std::vector<uint64_t>& lines, const crdt_hip_mark* m,
+                                        crdt_hip_line_info* info, bool* beyond) const {
+        return lines_get(
+            [&](const uint64_t* q, size_t n, LinePos* out, crdt_hip_line_info* i) {
+                return crdt_hip_oplog_line_starts(log_.get(), m, q, n, out, i);
+            },
+            nullptr, lines, info, beyond);
     }
     FormatSet formats_;
     struct Free {
@@ -464,6 +521,22 @@ public:
     std::string text_at(const Mark& m, size_t start = 0, size_t end = std::string::npos) const {
         return text_window(m.get(), start, end, false);
     }
+    // HipMerge::line_starts / lines_of / text_lines on the device (the queued updates are decoded
+    // first): a wave per query over the replica's kept document order, and only the lines' text comes
+    // back.  lines_of takes positions in the adapter's unit.
+    std::vector<LinePos> line_starts(const std::vector<uint64_t>& lines, const crdt_hip_mark* m = nullptr) const {
+        return line_starts_of(lines, m, nullptr, nullptr);
+    }
+    std::vector<LinePos> lines_of(const std::vector<uint64_t>& pos, const crdt_hip_mark* m = nullptr) const {
+        return lines_at(pos, m, false);
+    }
+    std::string text_lines(size_t first, size_t count, const crdt_hip_mark* m = nullptr) const {
+        return text_lines_get(
+            [&](const std::vector<uint64_t>& q, crdt_hip_line_info* info, bool* beyond) {
+                return line_starts_of(q, m, info, beyond);
+            },
+            [&](size_t a, size_t b) { return text_window(m, a, b, true); }, first, count);
+    }
     // HipMerge::anchor_at / resolve / resolve_many on the device (the queued updates are decoded
     // first): resolved in HIP kernels against the replica's kept document order.
     Anchor anchor_at(size_t pos, uint32_t bias = CRDT_HIP_ANCHOR_AFTER) const {
@@ -521,6 +594,24 @@ protected:
                 return crdt_hip_replica_text_at(dev_->ctx, rep_, m, s, e, flags, out, cap, n, info);
             },
             dev_->ctx, start, end, bytes, 1 << 16);
+    }
+    std::vector<LinePos> line_starts_of(const std::vector<uint64_t>& lines, const crdt_hip_mark* m,
+                                        crdt_hip_line_info* info, bool* beyond) const {
+        flush();
+        return lines_get(
+            [&](const uint64_t* q, size_t n, LinePos* out, crdt_hip_line_info* i) {
+                return crdt_hip_replica_line_starts(dev_->ctx, rep_, m, q, n, out, i);
+            },
+            dev_->ctx, lines, info, beyond);
+    }
+    std::vector<LinePos> lines_at(const std::vector<uint64_t>& pos, const crdt_hip_mark* m, bool bytes) const {
+        flush();
+        return lines_get(
+            [&](const uint64_t* q, size_t n, LinePos* out, crdt_hip_line_info* info) {
+                return crdt_hip_replica_lines_of(dev_->ctx, rep_, m, q, n, bytes ? (uint32_t)CRDT_HIP_TEXT_BYTES : 0u,
+                                                 out, info);
+            },
+            dev_->ctx, pos);
     }
     Anchor anchor_of(size_t pos, uint32_t bias, bool bytes) const {
         flush();
@@ -598,6 +689,10 @@ public:
     }
     std::string text_at(const Mark& m, size_t start = 0, size_t end = std::string::npos) const {
         return text_window(m.get(), start, end, true);
+    }
+    // Positions in byte offsets (one inside a codepoint is an error).
+    std::vector<LinePos> lines_of(const std::vector<uint64_t>& pos, const crdt_hip_mark* m = nullptr) const {
+        return lines_at(pos, m, true);
     }
     // Anchors taken at, and resolved to, byte offsets (one inside a codepoint is an error).
     Anchor anchor_at(size_t pos, uint32_t bias = CRDT_HIP_ANCHOR_AFTER) const {

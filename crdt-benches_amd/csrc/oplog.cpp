@@ -1040,6 +1040,103 @@ int OpLog::text_at(const LogMark* m, uint64_t start, uint64_t end, uint32_t flag
     return CRDT_HIP_OK;
 }
 
+// ---- the line index ----------------------------------------------------------------------------
+int line_check(const uint64_t* in, size_t n, uint32_t flags, const LinePos* out, std::string& err) {
+    if (flags & ~kTextBytes) {
+        err = "line flags are neither 0 nor BYTES";
+        return CRDT_HIP_EINVAL;
+    }
+    if (n && (!in || !out)) {
+        err = "null argument";
+        return CRDT_HIP_EINVAL;
+    }
+    if (n >= (1ull << 31)) {
+        err = "2^31 or more line queries";
+        return CRDT_HIP_ERANGE;
+    }
+    return CRDT_HIP_OK;
+}
+
+int line_check_version(bool lines, bool beyond, bool inside, std::string& err) {
+    if (beyond) {
+        err = lines ? "line number beyond the version" : "line position beyond the version";
+        return CRDT_HIP_ERANGE;
+    }
+    if (inside) {
+        err = "line position inside a codepoint";
+        return CRDT_HIP_EINVAL;
+    }
+    return CRDT_HIP_OK;
+}
+
+namespace {
+// A version's line index: ends[v] the UTF-8 bytes of its first v items (byte_ends, under the
+// version's selector), and per line k = 0..L its start in items; the entry L + 1 is the end.
+struct LineIndex {
+    std::vector<uint64_t> ends, starts;
+    LineInfo info{};
+};
+int line_index(const OpLog& log, const LogMark* m, LineIndex& x, std::string& err) {
+    std::vector<uint32_t> order;
+    err = log.document_order(order);
+    if (!err.empty()) return CRDT_HIP_EBADLOG;
+    x.ends.assign(1, 0);
+    x.starts.assign(1, 0);
+    for (uint32_t id : order) {
+        if (!in_version(log, m, id)) continue;
+        x.ends.push_back(x.ends.back() + utf8_len_cp(log.cp[id - 1]));
+        if (log.cp[id - 1] == kLineBreak) x.starts.push_back(x.ends.size() - 1);
+    }
+    x.info = LineInfo{(uint64_t)x.starts.size(), (uint64_t)x.ends.size() - 1, x.ends.back()};
+    x.starts.push_back(x.info.len);
+    return CRDT_HIP_OK;
+}
+}  // namespace
+
+int OpLog::line_starts(const LogMark* m, const uint64_t* lines, size_t n, LinePos* out, LineInfo* info,
+                       std::string& err) const {
+    if (int rc = mark_check(*this, m, err)) return rc;
+    if (int rc = line_check(lines, n, 0, out, err)) return rc;
+    LineIndex x;
+    if (int rc = line_index(*this, m, x, err)) return rc;
+    bool beyond = false;
+    for (size_t k = 0; k < n; ++k) beyond |= lines[k] > x.info.lines;
+    if (int rc = line_check_version(true, beyond, false, err)) return rc;
+    for (size_t k = 0; k < n; ++k) {
+        const uint64_t s = x.starts[(size_t)lines[k]];
+        out[k] = LinePos{lines[k], s, x.ends[(size_t)s], 0, 0};
+    }
+    if (info) *info = x.info;
+    return CRDT_HIP_OK;
+}
+
+int OpLog::lines_of(const LogMark* m, const uint64_t* pos, size_t n, uint32_t flags, LinePos* out,
+                    LineInfo* info, std::string& err) const {
+    if (int rc = mark_check(*this, m, err)) return rc;
+    if (int rc = line_check(pos, n, flags, out, err)) return rc;
+    const bool bytes = (flags & kTextBytes) != 0;
+    LineIndex x;
+    if (int rc = line_index(*this, m, x, err)) return rc;
+    const uint64_t total = bytes ? x.info.len_bytes : x.info.len;
+    bool beyond = false, inside = false;
+    for (size_t k = 0; k < n; ++k) beyond |= pos[k] > total;
+    std::vector<uint64_t> gap(n);  // items before each position
+    for (size_t k = 0; k < n && !beyond; ++k) {
+        gap[k] = pos[k];
+        if (bytes && !byte_rank(x.ends, pos[k], gap[k])) inside = true;
+    }
+    if (int rc = line_check_version(false, beyond, inside, err)) return rc;
+    for (size_t k = 0; k < n; ++k) {
+        // the line: the last of lines 0..L that starts at or before the gap
+        const size_t line =
+            (size_t)(std::upper_bound(x.starts.begin(), x.starts.end() - 1, gap[k]) - x.starts.begin()) - 1;
+        const uint64_t s = x.starts[line], sb = x.ends[(size_t)s];
+        out[k] = LinePos{(uint64_t)line, s, sb, gap[k] - s, x.ends[(size_t)gap[k]] - sb};
+    }
+    if (info) *info = x.info;
+    return CRDT_HIP_OK;
+}
+
 // ---- anchors -----------------------------------------------------------------------------------
 int anchor_check_at(const uint64_t* pos, const uint8_t* bias, size_t n, uint64_t visible,
                     std::string& err) {

@@ -152,6 +152,24 @@ int text_check(uint64_t start, uint64_t end, uint32_t flags, const size_t* out_l
 int text_check_window(uint64_t start, uint64_t end, uint64_t total, bool inside, const TextInfo& w,
                       const uint8_t* out, size_t cap, size_t* out_len, TextInfo* info, std::string& err);
 
+// The line index (crdt_hip_lines.h; the device twin is lines.hip).  Layouts of crdt_hip_line_pos
+// and crdt_hip_line_info.
+constexpr uint32_t kLineBreak = 0x0A;  // the one codepoint that ends a line
+struct LinePos {
+    uint64_t line, start, start_bytes, col, col_bytes;
+};
+struct LineInfo {
+    uint64_t lines, len, len_bytes;
+};
+// The checks of a line_starts / lines_of call that need no document, shared by the host and the
+// device path, in their order: flags other than 0 or kTextBytes, n > 0 with a null input array or
+// a null out (EINVAL); 2^31 or more queries (ERANGE, the bound of anchor_check_at).
+int line_check(const uint64_t* in, size_t n, uint32_t flags, const LinePos* out, std::string& err);
+// And those that need the version, in their order: `beyond` (a line number above L + 1, or a
+// position beyond the version in the unit asked; ERANGE), then `inside` (a byte position inside a
+// codepoint; EINVAL).
+int line_check_version(bool lines, bool beyond, bool inside, std::string& err);
+
 // Anchors (crdt_hip.h, "anchors"; the device twin is anchor.hip): a place in the text named by the
 // identity of the item next to it.  Layouts of crdt_hip_anchor and crdt_hip_anchor_pos.
 constexpr uint64_t kAnchorEdge = ~0ull;
@@ -290,6 +308,16 @@ public:
     // but ESPACE out, *out_len and *info are untouched.  out_len may be null only to be refused.
     int text_at(const LogMark* m, uint64_t start, uint64_t end, uint32_t flags, uint8_t* out,
                 size_t cap, size_t* out_len, TextInfo* info, std::string& err) const;
+    // The line index of a version (crdt_hip_lines.h): line numbers 0..L + 1 -> where each line
+    // starts, and gap positions (codepoints, or UTF-8 bytes with kTextBytes) -> line, line start
+    // and column.  The definition the device path (lines.hip) is held to: the order comes from
+    // document_order per call, O(items); the positional index is neither read nor touched.  The
+    // checks run in the order crdt_hip_lines.h states, from "fewer items than the mark" on; on any
+    // error out and *info are untouched.  info may be null; n == 0 writes only *info.
+    int line_starts(const LogMark* m, const uint64_t* lines, size_t n, LinePos* out, LineInfo* info,
+                    std::string& err) const;
+    int lines_of(const LogMark* m, const uint64_t* pos, size_t n, uint32_t flags, LinePos* out,
+                 LineInfo* info, std::string& err) const;
     // Local edits as a set of positional patches in the patches_since convention (crdt_hip.h,
     // "local edits"): validated up front (edit_plan, then the lamport bound and the positional
     // index), and a rejected call changes nothing; then remove + insert per patch, in order, which

@@ -341,6 +341,24 @@ int replica_text_at(Engine& E, Replica& r, const DeviceMark* m, uint64_t start, 
                     uint32_t flags, uint8_t* out, size_t cap, size_t* out_len, TextInfo* info,
                     TextStats* stats = nullptr);
 
+// The line index (lines.hip; semantics in crdt_hip_lines.h, host twins OpLog::line_starts and
+// OpLog::lines_of).
+struct LineStats {  // what the last device line_starts / lines_of observed (crdt_hip_line_stats)
+    uint64_t queries = 0;    // line numbers or positions of the call
+    uint64_t ranks = 0;      // ranks of the document order streamed (the items held)
+    uint64_t device_ns = 0;  // summed device time of the call's kernels (HIP events)
+};
+struct LinePos;
+struct LineInfo;
+// Both calls: q holds n line numbers (positions false; flags ignored) or n gap positions, in
+// codepoints or with kTextBytes in UTF-8 bytes.  Settles a pending decode, runs the checks of
+// crdt_hip_lines.h in their order (m null: the version now), brings r.inc up to date as
+// replica_merge_inc does, counts and scans codepoints, bytes and line breaks under the version's
+// predicate, seeks every query with a wave and waits once.  out and *info are written only by a
+// call that succeeds.
+int replica_lines(Engine& E, Replica& r, const DeviceMark* m, bool positions, const uint64_t* q, size_t n,
+                  uint32_t flags, LinePos* out, LineInfo* info, LineStats* stats = nullptr);
+
 // Incremental merge (incr.hip): the merged text (may be null), its UTF-8 bytes and codepoints;
 // *path = 1 when only the items appended since the previous merge_inc were ranked, 0 for a
 // full merge (the first call, a concurrent update, more than kIncMax new items, Fugue).
