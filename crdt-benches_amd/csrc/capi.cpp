@@ -21,6 +21,7 @@
 
 #include "crdt_hip.h"
 #include "crdt_hip_lines.h"
+#include "crdt_hip_utf16.h"
 #include "engine.hpp"
 #include "oplog.hpp"
 #include "replica.hpp"
@@ -46,6 +47,7 @@ struct crdt_hip_ctx {
     crdt::FormatStats last_format;  // what the last device spans observed
     crdt::TextStats last_text;      // what the last device text_at observed
     crdt::LineStats last_line;      // what the last device line_starts / lines_of observed
+    crdt::UnitStats last_unit;      // what the last device units_of observed, one inside a _utf16 call included
 };
 namespace {
 // Names the owner of a mark: every log and replica handle gets its own, a clone included.
@@ -1144,6 +1146,89 @@ int crdt_hip_replica_lines_of(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt
 int crdt_hip_line_stats(const crdt_hip_ctx* ctx, uint64_t* queries, uint64_t* ranks, uint64_t* device_ns) {
     if (!ctx) return null_ctx();
     const crdt::LineStats& s = ctx->last_line;
+    put(queries, s.queries, ranks, s.ranks, device_ns, s.device_ns);
+    return 0;
+}
+// ---- UTF-16 positions (crdt_hip_utf16.h): a gap in three units, edits and patches in UTF-16 --------
+static_assert(sizeof(crdt_hip_unit_pos) == sizeof(crdt::UnitPos) && sizeof(crdt_hip_unit_pos) == 24 &&
+                  sizeof(crdt_hip_unit_info) == sizeof(crdt::UnitInfo) && sizeof(crdt_hip_unit_info) == 24 &&
+                  CRDT_HIP_UNIT_CODEPOINTS == crdt::kUnitCodepoints && CRDT_HIP_UNIT_BYTES == crdt::kUnitBytes &&
+                  CRDT_HIP_UNIT_BYTES == CRDT_HIP_TEXT_BYTES && CRDT_HIP_UNIT_UTF16 == crdt::kUnitUtf16,
+              "unit layouts");
+int crdt_hip_oplog_units_of(crdt_hip_oplog* log, const crdt_hip_mark* m, const uint64_t* pos, size_t n,
+                            uint32_t unit, crdt_hip_unit_pos* out, crdt_hip_unit_info* info) {
+    if (int rc = check_log_mark(log, m, true, true)) return rc;
+    return host([&](std::string& e) {
+        return log->log.units_of(m ? &m->host : nullptr, pos, n, unit, reinterpret_cast<crdt::UnitPos*>(out),
+                                 reinterpret_cast<crdt::UnitInfo*>(info), e);
+    });
+}
+int crdt_hip_replica_units_of(crdt_hip_ctx* ctx, crdt_hip_replica* r, const crdt_hip_mark* m,
+                              const uint64_t* pos, size_t n, uint32_t unit, crdt_hip_unit_pos* out,
+                              crdt_hip_unit_info* info) {
+    return device(ctx, check_replica_mark(ctx, r, m, true, true), [&] {
+        return crdt::replica_units(ctx->eng, r->r, m ? &m->dev : nullptr, unit, pos, n,
+                                   reinterpret_cast<crdt::UnitPos*>(out),
+                                   reinterpret_cast<crdt::UnitInfo*>(info), &ctx->last_unit);
+    });
+}
+int crdt_hip_oplog_apply_patches_utf16(crdt_hip_oplog* log, const crdt_hip_patch* p, size_t n,
+                                       const uint8_t* ins, size_t ins_len, uint32_t* added,
+                                       uint32_t* tombstoned) {
+    if (!log || (!p && n) || (!ins && ins_len)) return null_arg(nullptr);
+    return host([&](std::string& e) {
+        return log->log.apply_patches_utf16(reinterpret_cast<const PatchRec*>(p), n, ins, ins_len, added,
+                                            tombstoned, e);
+    });
+}
+constexpr const char* kReplaceUtf16 = "replace of 2^32 or more UTF-16 code units or bytes";
+int crdt_hip_oplog_replace_utf16(crdt_hip_oplog* log, size_t start, size_t end, const char* utf8,
+                                 size_t nbytes) {
+    if (!log || (!utf8 && nbytes)) return null_arg(nullptr);
+    return replace_as_patch(nullptr, start, end, nbytes, kReplaceUtf16, [&](const crdt_hip_patch* one) {
+        return crdt_hip_oplog_apply_patches_utf16(log, one, 1, u8(utf8), nbytes, nullptr, nullptr);
+    });
+}
+int crdt_hip_oplog_patches_since_utf16(crdt_hip_oplog* log, const crdt_hip_mark* m,
+                                       crdt_hip_patch* out, size_t cap, size_t* out_n, uint8_t* ins,
+                                       size_t ins_cap, size_t* out_ins) {
+    if (int rc = check_log_mark(log, m, out_n && out_ins)) return rc;
+    return host([&](std::string& e) {
+        std::vector<PatchRec> p;
+        std::vector<uint8_t> text;
+        if (int rc = log->log.patches_since_utf16(m->host, p, text, e)) return rc;
+        return copy_out2(p, out, cap, out_n, text, ins, ins_cap, out_ins, false, e);
+    });
+}
+int crdt_hip_replica_apply_patches_utf16(crdt_hip_ctx* ctx, crdt_hip_replica* r,
+                                         const crdt_hip_patch* p, size_t n, const uint8_t* ins,
+                                         size_t ins_len, uint32_t* added, uint32_t* tombstoned) {
+    return device(ctx, check_replica(ctx, r, (p || !n) && (ins || !ins_len)), [&] {
+        return crdt::replica_apply_patches_utf16(ctx->eng, r->r, reinterpret_cast<const PatchRec*>(p), n, ins,
+                                                 ins_len, added, tombstoned, &ctx->last_edit,
+                                                 &ctx->last_unit);
+    });
+}
+int crdt_hip_replica_replace_utf16(crdt_hip_ctx* ctx, crdt_hip_replica* r, size_t start, size_t end,
+                                   const char* utf8, size_t nbytes) {
+    if (int rc = check_replica(ctx, r, utf8 || !nbytes)) return rc;
+    return replace_as_patch(ctx, start, end, nbytes, kReplaceUtf16, [&](const crdt_hip_patch* one) {
+        return crdt_hip_replica_apply_patches_utf16(ctx, r, one, 1, u8(utf8), nbytes, nullptr, nullptr);
+    });
+}
+int crdt_hip_replica_patches_since_utf16(crdt_hip_ctx* ctx, crdt_hip_replica* r,
+                                         const crdt_hip_mark* m, crdt_hip_patch* out, size_t cap,
+                                         size_t* out_n, uint8_t* ins, size_t ins_cap,
+                                         size_t* out_ins) {
+    return device(ctx, check_replica_mark(ctx, r, m, out_n && out_ins), [&] {
+        return crdt::replica_patches_since_utf16(ctx->eng, r->r, m->dev, reinterpret_cast<PatchRec*>(out), cap,
+                                                 out_n, ins, ins_cap, out_ins, &ctx->last_patch,
+                                                 &ctx->last_unit);
+    });
+}
+int crdt_hip_unit_stats(const crdt_hip_ctx* ctx, uint64_t* queries, uint64_t* ranks, uint64_t* device_ns) {
+    if (!ctx) return null_ctx();
+    const crdt::UnitStats& s = ctx->last_unit;
     put(queries, s.queries, ranks, s.ranks, device_ns, s.device_ns);
     return 0;
 }

@@ -18,6 +18,7 @@
 
 #include "crdt_hip.h"
 #include "crdt_hip_lines.h"
+#include "crdt_hip_utf16.h"
 
 namespace hipmerge {
 
@@ -122,6 +123,17 @@ std::string text_lines_get(Starts&& starts, Window&& window, size_t first, size_
                    nullptr, nullptr);
     }
     return window((size_t)s[0].start_bytes, (size_t)s[1].start_bytes);
+}
+
+// UTF-16 positions (crdt_hip_utf16.h): a gap in codepoints, UTF-8 bytes and UTF-16 code units.
+using UnitPos = crdt_hip_unit_pos;
+// call(positions, n, out, info) -> the n records.
+template <class Call>
+std::vector<UnitPos> units_get(Call&& call, crdt_hip_ctx* ctx, const std::vector<uint64_t>& q,
+                               crdt_hip_unit_info* info = nullptr) {
+    std::vector<UnitPos> out(q.size());
+    check(call(q.data(), q.size(), out.data(), info), ctx, "units_of");
+    return out;
 }
 
 // A cursor, a selection end: a place in the text that survives every edit and sync and means the
@@ -344,6 +356,28 @@ public:
             },
             [&](size_t a, size_t b) { return text_window(m, a, b, true); }, first, count);
     }
+    // UTF-16 positions (crdt_hip_utf16.h) for a caller that counts UTF-16 code units (a JavaScript
+    // string, LSP's `character`): the gaps `pos`, given in `unit` (CRDT_HIP_UNIT_*), in all three
+    // units, now (m null) or as of a mark; an edit and the patches since a mark in code units.
+    std::vector<UnitPos> units_of(const std::vector<uint64_t>& pos, uint32_t unit, const crdt_hip_mark* m = nullptr,
+                                  crdt_hip_unit_info* info = nullptr) const {
+        return units_get(
+            [&](const uint64_t* q, size_t n, UnitPos* out, crdt_hip_unit_info* i) {
+                return crdt_hip_oplog_units_of(log_.get(), m, q, n, unit, out, i);
+            },
+            nullptr, pos, info);
+    }
+    void replace_utf16(size_t start, size_t end, std::string_view s) {
+        check(crdt_hip_oplog_replace_utf16(log_.get(), start, end, s.data(), s.size()), nullptr,
+              "oplog_replace_utf16");
+    }
+    std::vector<Patch> patches_since_utf16(const Mark& m) const {
+        return patches_get(
+            [&](crdt_hip_patch* out, size_t cap, size_t* n, uint8_t* ins, size_t icap, size_t* nb) {
+                return crdt_hip_oplog_patches_since_utf16(log_.get(), m.get(), out, cap, n, ins, icap, nb);
+            },
+            nullptr, 0, 0);
+    }
     // The anchor of gap `pos` (bias: CRDT_HIP_ANCHOR_AFTER sticks to the item before the gap,
     // BEFORE to the one after it), and where anchors made here or on any peer lie now.
     Anchor anchor_at(size_t pos, uint32_t bias = CRDT_HIP_ANCHOR_AFTER) const {
@@ -536,6 +570,32 @@ public:
                 return line_starts_of(q, m, info, beyond);
             },
             [&](size_t a, size_t b) { return text_window(m, a, b, true); }, first, count);
+    }
+    // HipMerge::units_of / replace_utf16 / patches_since_utf16 on the device (the queued updates are
+    // decoded first): a wave per position over the replica's kept document order; the edit and the
+    // patches pay one such translation of their boundaries on top of the codepoint call.
+    std::vector<UnitPos> units_of(const std::vector<uint64_t>& pos, uint32_t unit, const crdt_hip_mark* m = nullptr,
+                                  crdt_hip_unit_info* info = nullptr) const {
+        flush();
+        return units_get(
+            [&](const uint64_t* q, size_t n, UnitPos* out, crdt_hip_unit_info* i) {
+                return crdt_hip_replica_units_of(dev_->ctx, rep_, m, q, n, unit, out, i);
+            },
+            dev_->ctx, pos, info);
+    }
+    void replace_utf16(size_t start, size_t end, std::string_view s) {
+        flush();
+        check(crdt_hip_replica_replace_utf16(dev_->ctx, rep_, start, end, s.data(), s.size()), dev_->ctx,
+              "replica_replace_utf16");
+    }
+    std::vector<Patch> patches_since_utf16(const Mark& m) const {
+        flush();
+        return patches_get(
+            [&](crdt_hip_patch* out, size_t cap, size_t* n, uint8_t* ins, size_t icap, size_t* nb) {
+                return crdt_hip_replica_patches_since_utf16(dev_->ctx, rep_, m.get(), out, cap, n, ins,
+                                                            icap, nb);
+            },
+            dev_->ctx, 4096, 1 << 16);
     }
     // HipMerge::anchor_at / resolve / resolve_many on the device (the queued updates are decoded
     // first): resolved in HIP kernels against the replica's kept document order.

@@ -1137,6 +1137,67 @@ int OpLog::lines_of(const LogMark* m, const uint64_t* pos, size_t n, uint32_t fl
     return CRDT_HIP_OK;
 }
 
+// ---- UTF-16 positions ----------------------------------------------------------------------------
+int unit_check(const uint64_t* pos, size_t n, uint32_t unit, const UnitPos* out, std::string& err,
+               uint64_t bound) {
+    if (unit > kUnitUtf16) {
+        err = "unit is neither CODEPOINTS, BYTES nor UTF16";
+        return CRDT_HIP_EINVAL;
+    }
+    if (n && (!pos || !out)) {
+        err = "null argument";
+        return CRDT_HIP_EINVAL;
+    }
+    if (n >= bound) {
+        err = "2^31 or more positions";
+        return CRDT_HIP_ERANGE;
+    }
+    return CRDT_HIP_OK;
+}
+
+int unit_check_version(uint32_t unit, bool beyond, bool inside, std::string& err) {
+    if (beyond) {
+        err = "position beyond the version";
+        return CRDT_HIP_ERANGE;
+    }
+    if (inside) {
+        err = unit == kUnitUtf16 ? "position inside a surrogate pair" : "position inside a codepoint";
+        return CRDT_HIP_EINVAL;
+    }
+    return CRDT_HIP_OK;
+}
+
+int OpLog::units_of(const LogMark* m, const uint64_t* pos, size_t n, uint32_t unit, UnitPos* out,
+                    UnitInfo* info, std::string& err, uint64_t bound) const {
+    if (int rc = mark_check(*this, m, err)) return rc;
+    if (int rc = unit_check(pos, n, unit, out, err, bound)) return rc;
+    std::vector<uint32_t> order;
+    err = document_order(order);
+    if (!err.empty()) return CRDT_HIP_EBADLOG;
+    // the one walk: per gap v (the first v selected items) its bytes and its UTF-16 code units
+    std::vector<uint64_t> eb(1, 0), e16(1, 0);
+    for (uint32_t id : order) {
+        if (!in_version(*this, m, id)) continue;
+        const uint32_t len = (uint32_t)utf8_len_cp(cp[id - 1]);
+        eb.push_back(eb.back() + len);
+        e16.push_back(e16.back() + utf16_units(len));
+    }
+    const UnitInfo total{(uint64_t)eb.size() - 1, eb.back(), e16.back()};
+    const std::vector<uint64_t>* ends = unit == kUnitBytes ? &eb : unit == kUnitUtf16 ? &e16 : nullptr;
+    const uint64_t len = ends ? ends->back() : total.len;
+    bool beyond = false, inside = false;
+    for (size_t k = 0; k < n; ++k) beyond |= pos[k] > len;
+    std::vector<uint64_t> gap(n);  // items before each position
+    for (size_t k = 0; k < n && !beyond; ++k) {
+        gap[k] = pos[k];
+        if (ends && !byte_rank(*ends, pos[k], gap[k])) inside = true;
+    }
+    if (int rc = unit_check_version(unit, beyond, inside, err)) return rc;
+    for (size_t k = 0; k < n; ++k) out[k] = UnitPos{gap[k], eb[(size_t)gap[k]], e16[(size_t)gap[k]]};
+    if (info) *info = total;
+    return CRDT_HIP_OK;
+}
+
 // ---- anchors -----------------------------------------------------------------------------------
 int anchor_check_at(const uint64_t* pos, const uint8_t* bias, size_t n, uint64_t visible,
                     std::string& err) {
@@ -1348,11 +1409,14 @@ int OpLog::spans(const FormatRec* f, size_t n, std::vector<SpanRec>& out, std::v
 }
 
 // ---- local edits as positional patches ---------------------------------------------------------
-// The argument-only checks of a patch array, in codepoints or (BYTES) in UTF-8 bytes: `visible`
-// and the non-touching rule are in the unit of pos and del.  emit(old position, del, first
-// codepoint, codepoints) per patch, the position in the document before the call.
+// The argument-only checks of a patch array, in the UNIT of pos and del (kUnit*): `visible` and the
+// non-touching rule are in that unit.  emit(old position, del, first codepoint, codepoints) per
+// patch, the position in the document before the call.  In UTF-16 code units no length is known
+// before the document is read: the range is left to the translation of the old positions, and the
+// item bound to the codepoint call that follows it (crdt_hip_utf16.h).
 namespace {
-template <bool BYTES, class Emit>
+constexpr const char* kPatchBeyond = "patch range beyond the document";
+template <uint32_t UNIT, class Emit>
 int plan_walk(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len, uint64_t visible,
               uint64_t items, std::vector<uint32_t>& cps, std::string& err, Emit&& emit) {
     cps.clear();
@@ -1379,18 +1443,22 @@ int plan_walk(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len, u
             return CRDT_HIP_EINVAL;
         }
         const uint64_t ncp = cps.size() - c0;
-        const uint64_t added = BYTES ? (uint64_t)r.ins_len : ncp;
+        uint64_t added = UNIT == kUnitBytes ? (uint64_t)r.ins_len : ncp;
+        if (UNIT == kUnitUtf16)
+            for (size_t c = c0; c < cps.size(); ++c) added += utf16_units(utf8_len_cp(cps[c])) - 1u;
         if (k && r.pos < next_min) {
             err = "patches are not ascending and non-touching";
             return CRDT_HIP_EINVAL;
         }
-        if (r.pos > len || r.del > len - r.pos) {
-            err = "patch range beyond the document";
-            return CRDT_HIP_ERANGE;
-        }
-        if (items + cps.size() >= 0x7FFFFFF0ull) {
-            err = "op log too large";
-            return CRDT_HIP_ERANGE;
+        if (UNIT != kUnitUtf16) {
+            if (r.pos > len || r.del > len - r.pos) {
+                err = kPatchBeyond;
+                return CRDT_HIP_ERANGE;
+            }
+            if (items + cps.size() >= 0x7FFFFFF0ull) {
+                err = "op log too large";
+                return CRDT_HIP_ERANGE;
+            }
         }
         emit((uint64_t)((int64_t)r.pos - shift), r.del, (uint32_t)c0, (uint32_t)ncp);
         len = len - r.del + added;
@@ -1406,7 +1474,7 @@ int edit_plan(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len, u
     plan.patch.clear();
     plan.ndel = 0;
     if (n < (1ull << 31)) plan.patch.reserve(n);
-    return plan_walk<false>(p, n, ins, ins_len, visible, items, plan.cps, err,
+    return plan_walk<kUnitCodepoints>(p, n, ins, ins_len, visible, items, plan.cps, err,
                             [&](uint64_t old_pos, uint32_t del, uint32_t c0, uint32_t ncp) {
                                 plan.patch.push_back(EditPatch{(uint32_t)old_pos, del, c0, ncp,
                                                                (uint32_t)plan.ndel, 0u});
@@ -1418,7 +1486,7 @@ int edit_plan_bytes(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_
                     uint64_t visible_bytes, uint64_t items, EditPlanBytes& plan, std::string& err) {
     plan.patch.clear();
     if (n < (1ull << 31)) plan.patch.reserve(n);
-    return plan_walk<true>(p, n, ins, ins_len, visible_bytes, items, plan.cps, err,
+    return plan_walk<kUnitBytes>(p, n, ins, ins_len, visible_bytes, items, plan.cps, err,
                            [&](uint64_t old_pos_b, uint32_t del_b, uint32_t c0, uint32_t ncp) {
                                plan.patch.push_back(BytePatch{old_pos_b, del_b, c0, ncp});
                            });
@@ -1456,6 +1524,116 @@ int OpLog::apply_patches_bytes(const PatchRec* p, size_t n, const uint8_t* ins, 
         shift += (int64_t)e.ncp - (int64_t)(v1 - v0);
     }
     return apply_patches(q.data(), n, ins, ins_len, added, tombstoned, err);
+}
+
+// ---- edits and patches in UTF-16 code units (crdt_hip_utf16.h) ---------------------------------
+int edit_plan_utf16(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
+                    EditPlanUtf16& plan, std::string& err) {
+    plan.bounds.clear();
+    plan.ncp.clear();
+    std::vector<uint32_t> cps;
+    return plan_walk<kUnitUtf16>(p, n, ins, ins_len, 0, 0, cps, err,
+                                 [&](uint64_t old_pos, uint32_t del, uint32_t, uint32_t ncp) {
+                                     plan.bounds.push_back(old_pos);
+                                     plan.bounds.push_back(old_pos + del);
+                                     plan.ncp.push_back(ncp);
+                                 });
+}
+
+int edit_patches_utf16(const EditPlanUtf16& plan, int rc_plan, const std::string& err_plan, int rc_units,
+                       const PatchRec* p, size_t n, const UnitPos* tr, std::vector<PatchRec>& q,
+                       std::string& err) {
+    if (rc_units == CRDT_HIP_ERANGE) {
+        err = kPatchBeyond;
+        return rc_units;
+    }
+    if (rc_units && rc_units != CRDT_HIP_EINVAL) return rc_units;  // (the document could not be read)
+    if (rc_plan) {
+        err = err_plan;
+        return rc_plan;
+    }
+    if (rc_units) {
+        err = "patch boundary inside a surrogate pair";
+        return rc_units;
+    }
+    q.resize(n);
+    int64_t shift = 0;  // codepoints inserted - deleted by the earlier patches
+    for (size_t k = 0; k < n; ++k) {
+        const uint64_t v0 = tr[2 * k].cp, v1 = tr[2 * k + 1].cp;
+        q[k] = PatchRec{(uint64_t)((int64_t)v0 + shift), p[k].ins_off, (uint32_t)(v1 - v0), p[k].ins_len};
+        shift += (int64_t)plan.ncp[k] - (int64_t)(v1 - v0);
+    }
+    return CRDT_HIP_OK;
+}
+
+int OpLog::apply_patches_utf16(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
+                               uint32_t* added, uint32_t* tombstoned, std::string& err) {
+    if (added) *added = 0;
+    if (tombstoned) *tombstoned = 0;
+    if (n == 0) return CRDT_HIP_OK;
+    EditPlanUtf16 plan;
+    std::string err_plan;
+    const int rc_plan = edit_plan_utf16(p, n, ins, ins_len, plan, err_plan);
+    std::vector<UnitPos> tr(plan.bounds.size());
+    const int rc_units = units_of(nullptr, plan.bounds.data(), plan.bounds.size(), kUnitUtf16, tr.data(),
+                                  nullptr, err, 1ull << 32);
+    std::vector<PatchRec> q;
+    if (int rc = edit_patches_utf16(plan, rc_plan, err_plan, rc_units, p, n, tr.data(), q, err)) return rc;
+    return apply_patches(q.data(), n, ins, ins_len, added, tombstoned, err);
+}
+
+namespace {
+// The codepoints and the UTF-16 code units of a piece of valid UTF-8.
+void utf8_units(const uint8_t* s, uint32_t len, uint64_t& ncp, uint64_t& n16) {
+    ncp = n16 = 0;
+    for (uint32_t i = 0; i < len; ++i) {
+        ncp += (s[i] & 0xC0u) != 0x80u;
+        n16 += (s[i] & 0xC0u) != 0x80u ? 1u + (s[i] >= 0xF0u) : 0u;
+    }
+}
+}  // namespace
+
+void since_bounds(const PatchRec* p, size_t n, const uint8_t* ins, std::vector<uint64_t>& bounds) {
+    bounds.resize(2 * n);
+    int64_t shift = 0;  // codepoints inserted - deleted by the earlier patches
+    for (size_t k = 0; k < n; ++k) {
+        uint64_t ncp = 0, n16 = 0;
+        if (p[k].ins_len) utf8_units(ins + p[k].ins_off, p[k].ins_len, ncp, n16);
+        bounds[2 * k] = (uint64_t)((int64_t)p[k].pos - shift);
+        bounds[2 * k + 1] = bounds[2 * k] + p[k].del;
+        shift += (int64_t)ncp - (int64_t)p[k].del;
+    }
+}
+
+int since_utf16(PatchRec* p, size_t n, const uint8_t* ins, const UnitPos* tr, std::string& err) {
+    for (size_t k = 0; k < n; ++k) {
+        if (tr[2 * k + 1].utf16 - tr[2 * k].utf16 >= (1ull << 32)) {
+            err = "a patch deletes 2^32 or more UTF-16 code units";
+            return CRDT_HIP_ERANGE;
+        }
+    }
+    int64_t shift = 0;  // UTF-16 code units inserted - deleted by the earlier patches
+    for (size_t k = 0; k < n; ++k) {
+        uint64_t ncp = 0, n16 = 0;
+        if (p[k].ins_len) utf8_units(ins + p[k].ins_off, p[k].ins_len, ncp, n16);
+        const uint64_t a = tr[2 * k].utf16, del = tr[2 * k + 1].utf16 - a;
+        p[k].pos = (uint64_t)((int64_t)a + shift);
+        p[k].del = (uint32_t)del;
+        shift += (int64_t)n16 - (int64_t)del;
+    }
+    return CRDT_HIP_OK;
+}
+
+int OpLog::patches_since_utf16(const LogMark& m, std::vector<PatchRec>& out, std::vector<uint8_t>& ins,
+                               std::string& err) const {
+    if (int rc = patches_since(m, out, ins, err)) return rc;
+    std::vector<uint64_t> bounds;
+    since_bounds(out.data(), out.size(), ins.data(), bounds);
+    std::vector<UnitPos> tr(bounds.size());
+    if (int rc = units_of(&m, bounds.data(), bounds.size(), kUnitCodepoints, tr.data(), nullptr, err,
+                          1ull << 32))
+        return rc == CRDT_HIP_ERANGE || rc == CRDT_HIP_EINVAL ? CRDT_HIP_EBADLOG : rc;
+    return since_utf16(out.data(), out.size(), ins.data(), tr.data(), err);
 }
 
 int OpLog::apply_patches(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,

@@ -170,6 +170,56 @@ int line_check(const uint64_t* in, size_t n, uint32_t flags, const LinePos* out,
 // codepoint; EINVAL).
 int line_check_version(bool lines, bool beyond, bool inside, std::string& err);
 
+// UTF-16 positions (crdt_hip_utf16.h; the device twin is utf16.hip).  Layouts of crdt_hip_unit_pos
+// and crdt_hip_unit_info; the units have the values of CRDT_HIP_UNIT_*.
+constexpr uint32_t kUnitCodepoints = 0, kUnitBytes = 1, kUnitUtf16 = 2;
+struct UnitPos {
+    uint64_t cp, bytes, utf16;
+};
+struct UnitInfo {
+    uint64_t len, len_bytes, len_utf16;
+};
+// An item's UTF-16 code units from its UTF-8 length (1..4): by value alone, 2 from U+10000 on.
+constexpr uint32_t utf16_units(uint32_t utf8_length) { return 1u + (utf8_length == 4u ? 1u : 0u); }
+// The checks of a units_of call that need no document, shared by the host and the device path, in
+// their order: a unit other than 0, 1, 2, n > 0 with a null pos or a null out (EINVAL); `bound` or
+// more positions (ERANGE; 2^31 at the boundary, the bound of anchor_check_at; the *_utf16 calls
+// translate two boundaries per patch of fewer than 2^31 patches).
+int unit_check(const uint64_t* pos, size_t n, uint32_t unit, const UnitPos* out, std::string& err,
+               uint64_t bound = 1ull << 31);
+// And those that need the version, in their order: `beyond` (a position beyond the version in the
+// unit asked; ERANGE), then `inside` (a byte position inside a codepoint, a UTF-16 position inside
+// a pair; EINVAL).
+int unit_check_version(uint32_t unit, bool beyond, bool inside, std::string& err);
+
+// Local edits in UTF-16 code units (crdt_hip_utf16.h), shared by the host and the device path.
+// The checks of a patch array that need no document, in array order and with the codes the header
+// states: all but the range, which the translation of `bounds` answers.  bounds: per patch that
+// passed, the two ends of the range it deletes in UTF-16 code units of the document before the call,
+// a = pos - sum over the earlier patches of (ins - del) and a + del; ncp: the codepoints it inserts.
+// A refusal is to be reported only if the translation finds none of `bounds` beyond the document
+// (the range check of an earlier patch comes first).
+struct EditPlanUtf16 {
+    std::vector<uint64_t> bounds;
+    std::vector<uint32_t> ncp;
+};
+int edit_plan_utf16(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
+                    EditPlanUtf16& plan, std::string& err);
+// What follows the translation of plan.bounds (rc_units and tr: what units_of answered for them in
+// kUnitUtf16; rc_plan and err_plan: what edit_plan_utf16 answered): ERANGE for a range beyond the
+// document, then the plan's own refusal, then EINVAL for a boundary inside a pair; otherwise q,
+// the n patches in codepoints for apply_patches.
+int edit_patches_utf16(const EditPlanUtf16& plan, int rc_plan, const std::string& err_plan, int rc_units,
+                       const PatchRec* p, size_t n, const UnitPos* tr, std::vector<PatchRec>& q,
+                       std::string& err);
+// Patches since a mark in UTF-16 code units, shared the same way.  since_bounds: per codepoint
+// patch of patches_since the two ends of what it deletes in codepoints of the mark's version (the
+// running shift undone).  since_utf16: with tr, their translation by units_of at the mark, pos and
+// del rewritten in place in UTF-16 code units; ERANGE when one patch's del reaches 2^32 (then p is
+// unchanged).
+void since_bounds(const PatchRec* p, size_t n, const uint8_t* ins, std::vector<uint64_t>& bounds);
+int since_utf16(PatchRec* p, size_t n, const uint8_t* ins, const UnitPos* tr, std::string& err);
+
 // Anchors (crdt_hip.h, "anchors"; the device twin is anchor.hip): a place in the text named by the
 // identity of the item next to it.  Layouts of crdt_hip_anchor and crdt_hip_anchor_pos.
 constexpr uint64_t kAnchorEdge = ~0ull;
@@ -331,6 +381,21 @@ public:
     // path is held to, not a product path: a call walks the whole document.
     int apply_patches_bytes(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
                             uint32_t* added, uint32_t* tombstoned, std::string& err);
+    // UTF-16 positions (crdt_hip_utf16.h).  units_of: n gap positions of a version in `unit` ->
+    // the same gaps in codepoints, UTF-8 bytes and UTF-16 code units, by one walk of
+    // document_order under the version's selector, O(items + n log items); the positional index is
+    // neither read nor touched.  The definition the device path (utf16.hip) is held to.  The checks
+    // run in the order crdt_hip_utf16.h states, from "fewer items than the mark" on (`bound`:
+    // unit_check's); on any error out and *info are untouched.  apply_patches_utf16 and
+    // patches_since_utf16 are built on it: edit_plan_utf16, the translation of the boundaries,
+    // edit_patches_utf16 and apply_patches; patches_since, since_bounds, the translation at the
+    // mark and since_utf16.
+    int units_of(const LogMark* m, const uint64_t* pos, size_t n, uint32_t unit, UnitPos* out,
+                 UnitInfo* info, std::string& err, uint64_t bound = 1ull << 31) const;
+    int apply_patches_utf16(const PatchRec* p, size_t n, const uint8_t* ins, size_t ins_len,
+                            uint32_t* added, uint32_t* tombstoned, std::string& err);
+    int patches_since_utf16(const LogMark& m, std::vector<PatchRec>& out, std::vector<uint8_t>& ins,
+                            std::string& err) const;
     // Anchors (crdt_hip.h, "anchors"): gap positions of the visible document -> identity-based
     // anchors (pos in codepoints, or with `bytes` in UTF-8 bytes; bias null: all AFTER), and
     // anchors -> where each lies now.  The definition the device path (anchor.hip) is held to: the

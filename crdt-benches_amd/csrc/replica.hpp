@@ -359,6 +359,34 @@ struct LineInfo;
 int replica_lines(Engine& E, Replica& r, const DeviceMark* m, bool positions, const uint64_t* q, size_t n,
                   uint32_t flags, LinePos* out, LineInfo* info, LineStats* stats = nullptr);
 
+// UTF-16 positions (utf16.hip; semantics in crdt_hip_utf16.h, host twin OpLog::units_of).
+struct UnitStats {  // what the last device translation observed (crdt_hip_unit_stats)
+    uint64_t queries = 0;    // positions of the call
+    uint64_t ranks = 0;      // ranks of the document order streamed (the items held)
+    uint64_t device_ns = 0;  // summed device time of the call's kernels (HIP events)
+};
+struct UnitPos;
+struct UnitInfo;
+// q holds n gap positions in `unit` (kUnit*, oplog.hpp).  Settles a pending decode, runs the checks
+// of crdt_hip_utf16.h in their order (m null: the version now; bound: unit_check's), brings r.inc up
+// to date as replica_merge_inc does, counts and scans codepoints, bytes and UTF-16 code units under
+// the version's predicate, seeks every position with a wave and waits once.  out and *info are
+// written only by a call that succeeds.
+int replica_units(Engine& E, Replica& r, const DeviceMark* m, uint32_t unit, const uint64_t* q, size_t n,
+                  UnitPos* out, UnitInfo* info, UnitStats* stats = nullptr, uint64_t bound = 1ull << 31);
+// The UTF-16 reading of apply_patches and patches_since (crdt_hip_utf16.h): compositions of one
+// replica_units call over the patches' boundaries and the codepoint call, which runs unchanged.
+// Each pays one more pass over the order and one more host wait than its codepoint call.  The
+// checks and the arithmetic are the host's (edit_plan_utf16, edit_patches_utf16, since_bounds,
+// since_utf16; oplog.hpp).  patches_since_utf16 writes out only with a code of 0 or ESPACE, except
+// that a call refused after the codepoint pass may leave codepoint patches in it.
+int replica_apply_patches_utf16(Engine& E, Replica& r, const PatchRec* p, size_t n, const uint8_t* ins,
+                                size_t ins_len, uint32_t* added, uint32_t* tombstoned,
+                                EditStats* stats = nullptr, UnitStats* ustats = nullptr);
+int replica_patches_since_utf16(Engine& E, Replica& r, const DeviceMark& m, PatchRec* out, size_t cap,
+                                size_t* out_n, uint8_t* ins, size_t ins_cap, size_t* out_ins,
+                                PatchStats* stats = nullptr, UnitStats* ustats = nullptr);
+
 // Incremental merge (incr.hip): the merged text (may be null), its UTF-8 bytes and codepoints;
 // *path = 1 when only the items appended since the previous merge_inc were ranked, 0 for a
 // full merge (the first call, a concurrent update, more than kIncMax new items, Fugue).
